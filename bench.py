@@ -5,10 +5,13 @@ Contract: python bench.py --gpus N --steps K --warmup W.  N > 1 runs one rank pe
 (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...: WORLD_SIZE is set and must equal N) or, when WORLD_SIZE
 is unset, this process starts them itself as a child `torch.distributed.run` BEFORE touching the GPU and relays rank 0's JSON line.
 Prints ONE JSON line on rank 0: metric tiles/sec on BASELINE.json configs[1] (B=256 tiles of 5x32x32x64 per GPU, K=512,
-d=64, bf16 activations, float32 master weights), plus
+d=64, bf16 activations, float32 master weights).  A plain run sets up, warms up, times exactly K steps and prints the line;
+--full adds the secondary measurements:
   * "roofline": the dominant kernel's achieved rate, timed live with HIP events on the launch stream;
   * "kernels":  per-kernel-family time shares from the same events (conv MFMA %, VQ HBM GB/s of the north star);
+  * "collapsed_codebook": the same step timed on the randn (collapsing) codebook, N=1 only;
   * "cpu_baseline": the CPU oracle (reference encoder math + oracle VQ/decoder) timed on this node's host cores, N=1 only.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ MFMA_BF16_PEAK_TF = 2500.0   # dense bf16
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256, help="tiles per GPU (weak scaling)")
     ap.add_argument("--codebook", type=int, default=512)
@@ -62,7 +65,16 @@ def parse():
     ap.add_argument("--extra", action="store_true",
                     help="N=1 only: also time BASELINE configs[3] (K=8192, d=128), configs[4] at one GPU (T=10, 64x64, two codebooks of 1024) "
                          "and the float32 parity mode of configs[1]; reported under \"extra\" (secondary lines, never `value`)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: instrumented per-kernel steps (kernels, gpu_kernels, vq_hbm, conv_mfma, roofline), "
+                         "the collapsed-codebook line and the CPU baseline; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its output dict and the parameters it left) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB; arrays above 2^20 elements as a fixed seeded sample")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -227,7 +239,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    timing = (not args.no_kernel_timing) and rank == 0
+    kernel_timing = args.full and not args.no_kernel_timing
+    timing = kernel_timing and rank == 0
     # auto: the captured graph on one GPU; N > 1 runs the eager data-parallel step (GPU-bound as well: ~1.5 ms of host time against a 2.5 ms
     # step) -- the capture of the RCCL all-reduces is verified bit for bit at one rank only (RCCL refuses two ranks on the single GPU of the
     # development box), so it stays opt-in (--graph on) until it has run on a multi-GPU node
@@ -235,8 +248,10 @@ def main():
     if args.graph == "on" and not graphed:
         raise SystemExit("bench.py: --graph on, but this trainer configuration cannot be captured (data-parallel reducer or a per-step lambda_vq)")
     dt, t_host, last = timed_steps(trainer, stream, args.steps, args.warmup, barrier, graphed)
+    if args.dump_outputs and rank == 0:              # before anything else steps the model
+        dump_outputs(args.dump_outputs, last, model)
     ksum, kern, ksteps = {}, {}, 0
-    if not args.no_kernel_timing:                     # separate instrumented steps: HIP events around every C-ABI call (rank 0)
+    if kernel_timing:                                 # separate instrumented steps: HIP events around every C-ABI call (rank 0)
         ksteps = max(2, min(5, args.steps))           # EVERY rank runs them: a step contains collectives
         model.concurrent_phase = False                # per-kernel spans are only meaningful without the two branches overlapping
         if timing:
@@ -347,7 +362,7 @@ def main():
         dom = max(ftime, key=lambda k: ftime[k][1])
         out["roofline"] = roofline_for(dom, ftime, args, model, n, s)
         args.steps = args.steps_timed
-    if world == 1 and args.codebook_init == "data" and not args.no_collapsed_line:
+    if args.full and world == 1 and args.codebook_init == "data" and not args.no_collapsed_line:
         # secondary line (never `value`): the same step on the randn codebook, whose assignment collapses to a few codes -- the regime
         # the earlier rounds' lines were measured in (the VQ kernel's re-evaluation share and histogram contention depend on it)
         m2, t2 = build_trainer(args, dev, dtype, args.codebook, args.emb_dim, args.phase_codebook, args.serial_streams, None)
@@ -360,11 +375,44 @@ def main():
     if world == 1 and args.extra:
         del trainer, stream, last
         out["extra"] = extra_lines(args, dev, barrier)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 1 << 20
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what a caller of the timed step receives -- every tensor (and float) of the step's output dict, and the
+    parameters the step left behind as `param.<name>` -- as <name>.npy.  Floating tensors are written as float32 (float64 stays
+    float64), integer and bool tensors as float64.  An array of more than DUMP_MAX_ELEMS elements is written as the flat elements at
+    a fixed set of positions (randperm with seed 0, sorted): the same positions for the same shape in every run."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach()
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            arrays[k] = torch.tensor(float(v), dtype=torch.float64)
+    for k, p in model.named_parameters():
+        arrays["param." + k] = p.detach()
+    res = {}
+    for name, t in arrays.items():
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        if t.numel() > DUMP_MAX_ELEMS:
+            sel = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[sel.to(t.device)]
+        res[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in res.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in res.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def mfma_util_from_profiles():

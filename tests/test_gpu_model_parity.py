@@ -206,6 +206,7 @@ def test_single_rank_rccl_reducer_path_matches_plain_trainer(golden_dir):
     tiles = torch.from_numpy(fx["tiles"]).float().to(DEV)
     plain = VQVAETrainer(_vqvae_from_fixture(fx), lr=1e-3, total_steps=10)
     ref = [plain.step(tiles[i])["loss"].item() for i in range(3)]
+    runs = []
     dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29731", rank=0, world_size=1, device_id=torch.device(DEV))
     try:
         m = _vqvae_from_fixture(fx)
@@ -226,7 +227,6 @@ def test_single_rank_rccl_reducer_path_matches_plain_trainer(golden_dir):
         # lambda_vq(step) schedule read from its device scalar at replay time.
         from frl_hip.training.schedules import LambdaVQSchedule
         seq = [tiles[0], tiles[1], bad, tiles[2], tiles[0]]
-        runs = []
         for graphed in (False, True):
             m2 = _vqvae_from_fixture(fx)
             sched = LambdaVQSchedule(lambda_vq=1.0, enable=True, schedule="linear", start=0, duration=4, floor=0.25, ceil=1.0)
@@ -242,6 +242,10 @@ def test_single_rank_rccl_reducer_path_matches_plain_trainer(golden_dir):
         for (n, p_), (_, q_) in zip(ma.named_parameters(), mb.named_parameters()):
             assert torch.equal(p_, q_), n
     finally:
+        # the graphs hold captured RCCL collectives of this communicator: release them before the process group shuts it down
+        torch.cuda.synchronize()
+        for _, t_, _ in runs:
+            t_.__dict__.pop("_graphs", None)
         dist.destroy_process_group()
     assert got == ref, (got, ref)
 

@@ -9,11 +9,11 @@ if [ "$quick" != notests ]; then
   python -m pytest tests -m gpu -x -q > $out/tests.log 2>&1 || { tail -30 $out/tests.log; exit 1; }
   tail -2 $out/tests.log
 fi
-python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 cat $out/bench.json
 [ "$quick" = quick ] && exit 0
 # profiled runs: eager launches (--graph off: one dispatch per kernel on the training streams) with the phase branch on the main stream
-P="--no-cpu-baseline --serial-streams --graph off"
+P="--full --no-cpu-baseline --serial-streams --graph off"
 rocprofv3 --kernel-trace --stats -d $out/prof -o run -- python3 bench.py --steps 20 --warmup 5 $P > $out/prof.log 2>&1 || { tail -20 $out/prof.log; exit 1; }
 rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch -o run -- python3 bench.py --steps 2 --warmup 1 --no-kernel-timing $P > $out/pmc_fetch.log 2>&1 || { tail -20 $out/pmc_fetch.log; exit 1; }
 rocprofv3 --pmc WRITE_SIZE -d $out/pmc_write -o run -- python3 bench.py --steps 2 --warmup 1 --no-kernel-timing $P > $out/pmc_write.log 2>&1 || { tail -20 $out/pmc_write.log; exit 1; }

@@ -38,7 +38,7 @@ def main():
     os.makedirs("profiles", exist_ok=True)
     stats, tot = kernel_stats(os.path.join(src, "prof", "run_results.db"))
     steps = max([st["calls"] for st in stats if "frl_adamw_kernel" in st["name"]] or [30])      # train steps in the profiled process
-    cmd = "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --serial-streams --graph off"
+    cmd = "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --serial-streams --graph off"
     with open(f"profiles/{name}_kernel_stats.csv", "w") as f:
         f.write("name,calls,total_ms,avg_us,min_us,max_us,pct,vgpr,agpr,sgpr,lds,scratch,grid,wg\n")
         for s in stats:
@@ -59,7 +59,7 @@ def main():
         w_kb = wr.get(k, (0, 0.0))[1]
         ks[k] = {"launches": fe.get(k, wr.get(k))[0], "FETCH_SIZE_KB_avg": round(f_kb, 2), "WRITE_SIZE_KB_avg": round(w_kb, 2),
                  "hbm_bytes_per_launch": int((2.0 * f_kb + w_kb) * 1024)}
-    json.dump({"note": "separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline "
+    json.dump({"note": "separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "
                        "--no-kernel-timing --serial-streams`; values in KiB averaged over the launches of each kernel; hbm_bytes_per_launch = (2*FETCH_SIZE + "
                        "WRITE_SIZE)*1024 (gfx950: FETCH_SIZE counts 128-B requests of wide coalesced reads as 64 B, MI355X_MICROARCH.md)",
                "kernels": ks}, open(f"profiles/{name}_pmc.json", "w"), indent=1)
@@ -88,7 +88,7 @@ def main():
                 cyc = sum(h["kernel_cycles"] for h in hits)
                 conv[fam] = round(busy / (cyc * 1024.0), 4)
         json.dump({"note": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE "
-                           "-- python3 bench.py --steps 2 --warmup 1 --no-kernel-timing --no-cpu-baseline --serial-streams --graph off; averages per "
+                           "-- python3 bench.py --full --steps 2 --warmup 1 --no-kernel-timing --no-cpu-baseline --serial-streams --graph off; averages per "
                            "launch; mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs): the share of SIMD cycles with the "
                            "matrix pipe busy (16 cycles per v_mfma_f32_16x16x32_bf16)",
                    "kernels": conv, "per_kernel": out}, open(f"profiles/{name}_mfma_util.json", "w"), indent=1)
