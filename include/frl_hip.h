@@ -283,6 +283,7 @@ int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* co
                       const float* const* gn_b, const float* const* gate_w, const float* const* gate_b, const float* head_w,
                       const float* head_b, void* y1, void* y2, void* y3, void* h, int64_t npix, int HW, int Ch, float eps, void* ws,
                       size_t ws_bytes, frl_stream_t stream);
+/* y1 = y2 = y3 = NULL: inference variant of the same launch (h only, bitwise the same h); a mix of NULL and non-NULL is an argument error. */
 /* The last block of the phase encoder together with the backward-data of the 1x1 phase head behind it (representation.py:169): `dh`
  * [B][5][HW][Ch] bf16 is the head's output gradient, head_w [Ch][64] float32, Ch in {4, 8, 12, 16}; dy = dh head_w is formed inside the
  * kernel on the matrix cores (float32, never written).  Same outputs as frl_tcn_hot_bwd; needs the two-subgroup kernel: no mask,
@@ -435,6 +436,14 @@ int frl_infonce_fwd(const float* emb, int D, const int64_t* pairs, const float* 
                     float* loss, frl_stream_t stream);
 int frl_infonce_pair_grads(const float* emb, int D, const int64_t* pairs, const float* sims, const float* coef, const float* gscale, int64_t T,
                            int64_t nseg, float temperature, int similarity, float* ga, float* gb, frl_stream_t stream);
+
+/* ---- code-map decoding (csrc/codes.hip) --------------------------------------------------------------------------------------
+ * frl_decode_codes: out[p][:] = table[idx[p]][:] for a decoded-code table [K][F] (dtype 0 = float32, 1 = bfloat16; the VQ-VAE decoder
+ * applied to the K codebook rows), idx [P] int32.  Indices in [-K, 0) wrap to idx + K; any other out-of-range index is clamped into
+ * [0, K) and ORs 1 into *index_flag (may be NULL).  P = 0 is a no-op.  Argument errors (P < 0, K <= 0, F <= 0, bad dtype, a NULL
+ * idx / table / out with P > 0) return a negative code before any HIP call.  16-byte copies whenever F * sizeof(T) is a multiple of 16. */
+int frl_decode_codes(const int32_t* idx, const void* table, void* out, int64_t P, int K, int F, int dtype, int32_t* index_flag,
+                     frl_stream_t stream);
 
 /* ---- mutual k-nearest-neighbour pair mining -----------------------------------------------------
  * frl/losses/pairs.py:531-610 pairs_mutual_knn_chunked: per anchor the k nearest anchors by L2 distance in feature space, excluding

@@ -254,6 +254,8 @@ struct ThChainArgs {
 };
 
 #define THC_IMG (32 * 64)                                          // fragments of one block's forward image (conv taps + gate)
+// KEEP = false: the inference variant, which writes h only (y1, y2, y3 exist for the backward; 3 x 168 MB of stores at cfg2)
+template <bool KEEP>
 __global__ __launch_bounds__(512, 2) void tcn_chain_fwd_kernel(const bf16* __restrict__ X, ThChainArgs a, int64_t npix, int HW, int Ch, float eps, int dyn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   frag8* wl = reinterpret_cast<frag8*>(smem);                      // [3][THC_IMG]
@@ -309,13 +311,13 @@ __global__ __launch_bounds__(512, 2) void tcn_chain_fwd_kernel(const bf16* __res
     asm volatile("" : "+v"(lw), "+s"(z0));                        // opaque per tile: neither the weight fragments nor the 3 x 48 per-channel
     const float* tb_ = tab + z0;                                  // constants are hoisted out of the tile loop into registers
     th_block_regs<1>(x, wl, wl + 24 * 64, tb_, lw, kc, eps);
-    if (valid) {
+    if (KEEP && valid) {
 #pragma unroll
       for (int t = 0; t < TH_T; ++t) th_store(a.y[0] + r0 + (int64_t)t * HW * 64, x[t]);
     }
     __builtin_amdgcn_sched_barrier(0);                             // (one block at a time: interleaved, the three bodies do not fit the register file)
     th_block_regs<2>(x, wl + THC_IMG, wl + THC_IMG + 24 * 64, tb_ + 256, lw, kc, eps);
-    if (valid) {
+    if (KEEP && valid) {
 #pragma unroll
       for (int t = 0; t < TH_T; ++t) th_store(a.y[1] + r0 + (int64_t)t * HW * 64, x[t]);
     }
@@ -327,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void tcn_chain_fwd_kernel(const bf16* __res
     const int64_t hrow = (r0 - 16 * kc) / 64 * Ch + 4 * kc;
 #pragma unroll
     for (int t = 0; t < TH_T; ++t) {
-      if (valid) th_store(a.y[2] + r0 + (int64_t)t * HW * 64, x[t]);
+      if (KEEP && valid) th_store(a.y[2] + r0 + (int64_t)t * HW * 64, x[t]);
       f32x4 ha = mfma16(wlh[lw], x[t].f[0], hb4);
       ha = mfma16(wlh[64 + lw], x[t].f[1], ha);
       if (valid && 4 * kc < Ch)
@@ -839,6 +841,7 @@ int frl_tcn_hot_fwd(const void* x, const void* drop_mask, const float* conv_w, c
 
 // The dense phase chain forward in one launch: x [B][5][HW][64] -> y1, y2, y3 (outputs of the blocks with dilation 1, 2, 4; same shape) and
 // h [B][5][HW][Ch] = head_w y3 + head_b (Ch <= 16, a multiple of 4).  Block parameters as in frl_tcn_hot_fwd, one set per block.
+// y1 = y2 = y3 = NULL selects the inference variant (h only, same arithmetic); a mix of NULL and non-NULL outputs is an argument error.
 size_t frl_tcn_chain_fwd_workspace_bytes(void) { return 3 * TH_PACK_BYTES + 4096; }
 // A/B hook: 1 = every wave walks its own fixed tile sequence (the round-3 first version), 0 (default) = tiles handed out by an LDS counter
 static int g_thc_static = 0;
@@ -849,6 +852,10 @@ int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* co
   if (npix <= 0 || HW <= 0) return frl_fail(-2, "tcn_chain_fwd: empty input");
   if (Ch < 4 || Ch > 16 || (Ch & 3)) return frl_fail(-2, "tcn_chain_fwd: head width must be 4, 8, 12 or 16");
   if (ws == nullptr || ws_bytes < frl_tcn_chain_fwd_workspace_bytes()) return frl_fail(-4, "tcn_chain_fwd: workspace too small");
+  const int n_keep = (y1 != nullptr) + (y2 != nullptr) + (y3 != nullptr);
+  if (n_keep != 0 && n_keep != 3) return frl_fail(-2, "tcn_chain_fwd: y1, y2, y3 must be all set (training) or all NULL (inference)");
+  if (h == nullptr) return frl_fail(-1, "tcn_chain_fwd: h is NULL");
+  const bool keep = n_keep == 3;
   ThChainArgs a;
   char* w = (char*)ws;
   for (int b = 0; b < 3; ++b) {
@@ -868,8 +875,13 @@ int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* co
   int64_t g = ((npix + 15) / 16 + 7) / 8;
   if (g > 256) g = 256;
   const size_t lds = (size_t)(3 * THC_IMG + 2 * 64) * sizeof(frag8) + (3 * 256 + 16) * sizeof(float) + 16;      // (+ the tile counter)
-  FRL_HIP(hipFuncSetAttribute((const void*)tcn_chain_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  FRL_LAUNCH(tcn_chain_fwd_kernel, dim3((unsigned)g), dim3(512), lds, stream, (const bf16*)x, a, npix, HW, Ch, eps, g_thc_static ? 0 : 1);
+  if (keep) {
+    FRL_HIP(hipFuncSetAttribute((const void*)tcn_chain_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FRL_LAUNCH_AS("tcn_chain_fwd_kernel", tcn_chain_fwd_kernel<true>, dim3((unsigned)g), dim3(512), lds, stream, (const bf16*)x, a, npix, HW, Ch, eps, g_thc_static ? 0 : 1);
+  } else {
+    FRL_HIP(hipFuncSetAttribute((const void*)tcn_chain_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FRL_LAUNCH_AS("tcn_chain_fwd_kernel<false>", tcn_chain_fwd_kernel<false>, dim3((unsigned)g), dim3(512), lds, stream, (const bf16*)x, a, npix, HW, Ch, eps, g_thc_static ? 0 : 1);
+  }
   return frl_check_launch("tcn_chain_fwd");
 }
 

@@ -136,9 +136,11 @@ class RepresentationModel(nn.Module):
         h = self.encoder(self._rows(x))
         return self.spatial_conv(h, return_gate=return_gate)
 
-    def _phase_chain(self, x: torch.Tensor) -> torch.Tensor:
+    def _phase_chain(self, x: torch.Tensor, inference: bool = False) -> torch.Tensor:
         """phase_tcn -> phase_head on [B,T,HW..,C] rows.  Hot configuration (bf16, three 64-channel blocks with dilation 1, 2, 4, T = 5,
-        no active Dropout1d, a head of <= 16 channels): one forward launch for the whole chain (Fh.TcnChainHeadFn)."""
+        no active Dropout1d, a head of <= 16 channels): one forward launch for the whole chain (Fh.TcnChainHeadFn).
+        inference=True (no autograd graph wanted): the launch skips the block outputs the backward would need (ops.tcn_chain_fwd
+        with keep_intermediates=False)."""
         tcn, head = self.phase_tcn, self.phase_head
         layers = list(tcn.layers)
         drop = any(self.training and l.dropout.p > 0.0 for l in layers)
@@ -146,14 +148,18 @@ class RepresentationModel(nn.Module):
             blocks = [(l.conv.weight, l.conv.bias, l.norm.weight, l.norm.bias, l.gate.weight, l.gate.bias, l.dilation, l.norm.num_groups,
                        l.needs_projection) for l in layers]
             if ops.tcn_chain_supported(x, blocks, head.weight):
+                if inference:
+                    return ops.tcn_chain_fwd(x, blocks, head.weight.detach(), head.bias.detach(), layers[0].norm.eps,
+                                             keep_intermediates=False)[3]
                 flat = [t for blk in blocks for t in blk[:6]]
                 return Fh.TcnChainHeadFn.apply(x, *flat, head.weight, head.bias, layers[0].norm.num_groups, layers[0].norm.eps)
         return head(tcn(x))
 
-    def forward_phase_nhwc(self, x_phase: torch.Tensor, z_type: torch.Tensor, return_parts: bool = False):
-        """x_phase [B,T,H,W,C_phase], z_type [B,H,W,d] (caller stop-grads) -> z_phase [B,T,H,W,zp]."""
+    def forward_phase_nhwc(self, x_phase: torch.Tensor, z_type: torch.Tensor, return_parts: bool = False, inference: bool = False):
+        """x_phase [B,T,H,W,C_phase], z_type [B,H,W,d] (caller stop-grads) -> z_phase [B,T,H,W,zp].
+        inference=True: forward only (the caller runs under no_grad), the phase chain skips what only its backward reads."""
         self._require_gpu(x_phase)
-        h = self._phase_chain(self._rows(x_phase))
+        h = self._phase_chain(self._rows(x_phase), inference=inference)
         zt = self._rows(z_type)
         film = self.phase_film
         gn, bn = film.gamma_network, film.beta_network

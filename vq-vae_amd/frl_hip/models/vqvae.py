@@ -272,6 +272,76 @@ class VQVAE(RepresentationModel):
                 self.commit_codebook_hooks()
         return out
 
+    # ------------------------------------------------------------------ inference: tiles -> code maps -> reconstructions
+    @torch.no_grad()
+    def encode_tiles(self, tile: torch.Tensor, mask: Optional[torch.Tensor] = None, return_latents: bool = False) -> Dict[str, torch.Tensor]:
+        """tile [B,T,H,W,F] -> dict(idx int32 [B,H,W], counts int32 [K], perplexity[, idx_phase int32 [B,T,H,W], counts_phase,
+        perplexity_phase][, valid bool [B,H,W]][, z_type, z_phase]).
+
+        The codes `forward_tiles` assigns, without its training-only work: no decoders, no losses, no autograd graph, eval semantics
+        (no dropout) whatever self.training is, and nothing is mutated -- no EMA statistics, no codebook-manager window, no
+        quant.last_counts / last_stats, no RNG draw.  The phase path runs only when a phase codebook exists or return_latents asks
+        for z_phase; its chain then skips the intermediates only the backward reads.  `valid` (mask given) follows the type loss: a
+        pixel is valid when it is valid at every time step."""
+        self._require_gpu(tile)
+        was_training = self.training
+        self.eval()
+        try:
+            tile = self._rows(tile)
+            b, t, hh, ww, f = tile.shape
+            z_type = self.forward_nhwc(ops.mean_time(tile))                  # [B,H,W,d]
+            d = z_type.shape[-1]
+            rows = z_type.reshape(-1, d)
+            q = self.quant
+            idx, _, stats, counts = ops.vq_assign(rows, q.codebook.detach(), q.prepared(rows.dtype, rows.shape[0]))
+            out = dict(idx=idx.reshape(b, hh, ww), counts=counts, perplexity=stats.narrow(0, 1, 1).reshape(()))
+            want_phase = self.phase and (hasattr(self, "quant_phase") or return_latents)
+            z_phase = self.forward_phase_nhwc(tile, z_type, inference=True) if want_phase else None
+            if z_phase is not None and hasattr(self, "quant_phase"):
+                qp = self.quant_phase
+                prow = z_phase.reshape(-1, z_phase.shape[-1])
+                pidx, _, pstats, pcounts = ops.vq_assign(prow, qp.codebook.detach(), qp.prepared(prow.dtype, prow.shape[0]))
+                out.update(idx_phase=pidx.reshape(b, t, hh, ww), counts_phase=pcounts, perplexity_phase=pstats.narrow(0, 1, 1).reshape(()))
+            if mask is not None:
+                m = mask.to(torch.uint8)
+                out["valid"] = (m.amin(dim=1) if m.dim() == 4 else m).to(torch.bool)
+            if return_latents:
+                out["z_type"] = z_type
+                if z_phase is not None:
+                    out["z_phase"] = z_phase
+            return out
+        finally:
+            self.train(was_training)
+
+    def _code_table(self, q: "VectorQuantizer", dec: Conv2DHead) -> torch.Tensor:
+        """Decoded codebook [K, F] in the compute dtype: the decoder applied to round_T(E), routed exactly as `_decode_loss` routes
+        forward_tiles' z_q (fused decoder kernel in the hot configuration, the modular 1x1 convolutions otherwise).  Every output row of
+        those kernels depends on its own input row only, so row k is the reconstruction forward_tiles produces for a pixel of code k."""
+        rows = q.codebook.detach().to(self.compute_dtype).contiguous()
+        l0, l2 = dec.layers[0], dec.layers[-1]
+        if (len(dec.layers) == 3 and self.fused_decoder
+                and ops.decoder_mse_supported(rows.shape[-1], l0.out_channels, l2.out_channels, rows)):
+            w1 = l0.weight.detach().reshape(l0.out_channels, l0.in_channels)
+            w2 = l2.weight.detach().reshape(l2.out_channels, l2.in_channels)
+            target = torch.zeros(rows.shape[0], l2.out_channels, dtype=rows.dtype, device=rows.device)   # (only the loss reads it)
+            return ops.decoder_mse_fwd(rows, w1, l0.bias.detach(), w2, l2.bias.detach(), target, None, want_xhat=True)[1]
+        return dec(rows)
+
+    @torch.no_grad()
+    def decode_codes(self, idx: Optional[torch.Tensor] = None, idx_phase: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Code maps -> reconstructions: idx [...] (type codes) -> xhat_type [..., F]; idx_phase [...] (phase codes) -> xhat_phase [..., F];
+        int32 or int64, in the compute dtype.  The decoder runs on the K codebook rows (a table rebuilt on every call from the current
+        codebook and decoder weights) and the pixels are a row gather from it (ops.decode_codes).  Reconstructions are in the normalised
+        feature space the model was trained in (training.export.denormalize maps them back)."""
+        out: Dict[str, torch.Tensor] = {}
+        if idx is not None:
+            out["xhat_type"] = ops.decode_codes(idx, self._code_table(self.quant, self.decoder_type))
+        if idx_phase is not None:
+            if not hasattr(self, "quant_phase"):
+                raise ValueError("decode_codes: idx_phase given but the model has no phase codebook (phase_codebook_size=0)")
+            out["xhat_phase"] = ops.decode_codes(idx_phase, self._code_table(self.quant_phase, self.decoder_phase))
+        return out
+
     @torch.no_grad()
     def init_codebook_from_tiles(self, tile: torch.Tensor, seed: int = 0) -> None:
         """Data-dependent codebook initialisation: every code starts on the encoder output of a pixel drawn (seeded, without

@@ -970,15 +970,16 @@ def tcn_chain_supported(x: torch.Tensor, blocks, head_w: torch.Tensor) -> bool:
 
 
 @_timed("tcn_chain_fwd")
-def tcn_chain_fwd(x, blocks, head_w, head_b, eps: float = 1e-5):
-    """x [B,5,HW..,64] -> (y1, y2, y3 [same shape], h [B,5,HW..,Ch])."""
+def tcn_chain_fwd(x, blocks, head_w, head_b, eps: float = 1e-5, keep_intermediates: bool = True):
+    """x [B,5,HW..,64] -> (y1, y2, y3 [same shape], h [B,5,HW..,Ch]).  keep_intermediates=False runs the inference variant of the
+    launch: y1, y2, y3 (kept for the backward only) are neither allocated nor written and come back as None; h is the same, bit for bit."""
     b, t, c = x.shape[0], x.shape[1], x.shape[-1]
     hw = x.numel() // (b * t * c)
     _chk_rows(x, c, "tcn_chain_fwd.x")
     ch = head_w.shape[0]
     lib = _lib.load()
     ws = workspace(lib.frl_tcn_chain_fwd_workspace_bytes(), x.device)
-    ys = [torch.empty_like(x) for _ in range(3)]
+    ys = [torch.empty_like(x) for _ in range(3)] if keep_intermediates else [None] * 3
     h = torch.empty(x.shape[:-1] + (ch,), dtype=x.dtype, device=x.device)
     arr = ctypes.c_void_p * 3
     cols = [arr(*[_f32(blk[i] if i != 4 else blk[i].reshape(c, c), "tcn parameter").data_ptr() for blk in blocks]) for i in range(6)]
@@ -1123,6 +1124,49 @@ def decoder_mse_bwd(z, w1, b1, w2, b2, target, mask, gscale, stats):
     check(lib.frl_decoder_mse_bwd(_p(z), _p(w1), _p(b1), _p(w2), _p(b2), _p(target), _p(mask), _p(gscale), _p(stats), _p(dz), _p(dw1),
                                   _p(db1), _p(dw2), _p(db2), p, cz, _p(ws), ws.numel(), _stream()), "frl_decoder_mse_bwd")
     return dz, dw1, db1, dw2, db2
+
+
+# ----------------------------------------------------------------------------------------------
+# code-map decoding (csrc/codes.hip)
+# ----------------------------------------------------------------------------------------------
+def _index_flag(device) -> torch.Tensor:
+    """The per-device word that `index_errors()` reads (see sanitize_indices)."""
+    device = torch.device(device)
+    flag = _INDEX_FLAG.get(device)
+    if flag is None:
+        flag = _INDEX_FLAG[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return flag
+
+
+@_timed("decode_codes")
+def decode_codes(idx: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """idx [...] int32 | int64 codes, table [K, F] float32 | bfloat16 (decoded codebook rows) -> table[idx] [..., F] in table.dtype.
+    Out-of-range indices follow the sparse-op convention (sanitize_indices), inside the kernel: [-K, 0) wraps, anything else is clamped
+    and flagged for `index_errors()`; with FRL_HIP_CHECK_INDICES=1 this call raises IndexError on the spot (one sync per call)."""
+    import os
+    if table.dim() != 2:
+        raise ValueError(f"decode_codes: table must be [K, F], got {tuple(table.shape)}")
+    k, f = table.shape
+    _chk_rows(table, f, "decode_codes.table")
+    if not idx.is_cuda or idx.device != table.device:
+        raise _lib.FrlHipError("decode_codes: idx must live on the table's GPU (no CPU fallback)")
+    if idx.dtype == torch.int64:
+        idx = idx.clamp(-k - 1, k).to(torch.int32)                  # (out-of-range stays out of range, and fits int32)
+    elif idx.dtype != torch.int32:
+        raise TypeError(f"decode_codes: idx must be int32 or int64, got {idx.dtype}")
+    idx = idx.contiguous()
+    out = torch.empty(tuple(idx.shape) + (f,), dtype=table.dtype, device=table.device)
+    p = idx.numel()
+    if p == 0:
+        return out
+    check_now = os.environ.get("FRL_HIP_CHECK_INDICES", "0") == "1"
+    flag = torch.zeros(1, dtype=torch.int32, device=table.device) if check_now else _index_flag(table.device)
+    check(_lib.load().frl_decode_codes(_p(idx), _p(table), _p(out), p, k, f, _dt(table), _p(flag), _stream()), "frl_decode_codes")
+    if check_now:
+        _index_flag(table.device).bitwise_or_(flag)
+        if bool(flag.item()):
+            raise IndexError(f"decode_codes: code index out of range for {k} codes")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

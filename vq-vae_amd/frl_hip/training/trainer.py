@@ -340,6 +340,80 @@ class VQVAETrainer:
                     qz.prepared(qz._prepared[0][2], 1 << 20)
         return out
 
+    @torch.no_grad()
+    def evaluate(self, batches, max_batches: Optional[int] = None) -> Dict:
+        """Validation pass (frl/training/representation/loops.py:307-420, validate_epoch): eval-mode `forward_tiles` under no_grad over
+        `batches` (tile tensors or {"tile", "mask"} dicts, as TilePrefetcher yields them), at most `max_batches` of them.
+
+        Returns the means over the batches whose loss is finite (loss, l_type, l_phase, vq_loss), `batches` / `skipped` counts,
+        `counts` int64 [K] summed over all batches with `perplexity` and `codes_used` taken from it (likewise `counts_phase`,
+        `perplexity_phase`, `codes_used_phase` with a phase codebook), and `sums` -- the raw device sums (loss terms over finite
+        batches, finite-batch count, batch count, code counts) for a caller that all-reduces them across ranks.  Everything is
+        accumulated on the device; the host synchronises once, at the end.
+
+        Nothing of the training state moves: parameters, optimizer state, EMA buffers, the codebook manager's window, step_idx,
+        quant.last_counts / last_stats and the model's training flag are as before, and captured step graphs stay valid (the phase
+        branch runs on the current stream here, so the side stream's workspace that a captured step uses is never regrown)."""
+        m = self.model
+        quants = m._quantizers() if hasattr(m, "_quantizers") else []
+        saved_q = [(q.last_counts, q.last_stats) for q in quants]
+        was_training, conc = m.training, getattr(m, "concurrent_phase", None)
+        acc = counts = counts_p = None
+        n_batches = 0
+        m.eval()
+        if conc is not None:
+            m.concurrent_phase = False
+        try:
+            for i, batch in enumerate(batches):
+                if max_batches is not None and i >= max_batches:
+                    break
+                tile, mask = (batch["tile"], batch.get("mask")) if isinstance(batch, dict) else (batch, None)
+                out = m.forward_tiles(tile, mask)
+                terms = [out["loss"], out["l_type"], out.get("l_phase"), out.get("vq_loss")]
+                dev = out["loss"].device
+                vals = torch.stack([torch.zeros((), dtype=torch.float64, device=dev) if v is None else v.detach().reshape(()).double()
+                                    for v in terms])
+                ok = torch.isfinite(vals[0]).reshape(1)
+                row = torch.cat([torch.where(ok, vals, torch.zeros_like(vals)), ok.double(), torch.ones(1, dtype=torch.float64, device=dev)])
+                acc = row if acc is None else acc + row
+                c = quants[0].last_counts.to(torch.int64)
+                counts = c if counts is None else counts + c
+                if len(quants) > 1 and out.get("idx_phase") is not None:
+                    cp = quants[1].last_counts.to(torch.int64)
+                    counts_p = cp if counts_p is None else counts_p + cp
+                n_batches += 1
+        finally:
+            m.train(was_training)
+            if conc is not None:
+                m.concurrent_phase = conc
+            for q, (lc, ls) in zip(quants, saved_q):
+                q.last_counts, q.last_stats = lc, ls
+
+        res: Dict = dict(loss=0.0, l_type=0.0, l_phase=0.0, vq_loss=0.0, batches=0, skipped=0)
+        if n_batches == 0:
+            return res
+        parts = [acc] + [x.double() for x in (counts, counts_p) if x is not None]
+        host = torch.cat(parts).cpu().split([t.numel() for t in parts])                 # the one host synchronisation
+        a = host[0]
+        n_ok = int(a[4].item())
+        for j, name in enumerate(("loss", "l_type", "l_phase", "vq_loss")):
+            res[name] = float(a[j].item()) / n_ok if n_ok else 0.0
+        res.update(batches=n_ok, skipped=n_batches - n_ok)
+
+        def usage(cnt_host: torch.Tensor, cnt_dev: torch.Tensor, suffix: str):
+            p = cnt_host / max(float(cnt_host.sum().item()), 1.0)
+            nz = p[p > 0]
+            res["counts" + suffix] = cnt_dev
+            res["perplexity" + suffix] = float(torch.exp(-(nz * nz.log()).sum()).item()) if nz.numel() else 0.0
+            res["codes_used" + suffix] = int((cnt_host > 0).sum().item())
+
+        usage(host[1], counts, "")
+        if counts_p is not None:
+            usage(host[2], counts_p, "_phase")
+        res["sums"] = dict(terms=acc[:4], finite_batches=acc[4], batches=acc[5], counts=counts,
+                           **({"counts_phase": counts_p} if counts_p is not None else {}))
+        return res
+
     def step(self, tile: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         lr_now = cosine_lr(self.step_idx, self.total_steps, self.lr, self.min_lr)
         for g in self.opt.param_groups:
