@@ -19,6 +19,19 @@ def _c(t: Optional[torch.Tensor]):
     return None if t is None else (t if t.is_contiguous() else t.contiguous())
 
 
+def _wanted(ctx, first: int, grads):
+    """grads[i] is the gradient of forward input first + i: those autograd does not want (a frozen parameter) come back as None, and
+    the tensors the kernels computed anyway are handed to ops.discard (inside ops.deferred_reductions their parked reductions still write
+    them at the flush)."""
+    out = []
+    for i, g in enumerate(grads):
+        if g is not None and not ctx.needs_input_grad[first + i]:
+            ops.discard(g)
+            g = None
+        out.append(g)
+    return tuple(out)
+
+
 class Conv1x1Fn(Function):
     """y = act(x W^T + b) over rows; W [Cout, Cin(,1,1)]."""
 
@@ -38,8 +51,8 @@ class Conv1x1Fn(Function):
         dx = ops.conv1x1_bwd_data(dy, w, y, ctx.act) if ctx.needs_input_grad[0] else None
         dw = db = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dw, db = ops.conv1x1_bwd_weight(dy, x, y, ctx.act, want_bias=ctx.has_bias)
-            dw = dw.reshape(w.shape)
+            dw, db = ops.conv1x1_bwd_weight(dy, x, y, ctx.act, want_bias=ctx.has_bias and ctx.needs_input_grad[2])
+            dw, = _wanted(ctx, 1, (dw.reshape(w.shape),))        # (the kernel always writes dW: a bias-only gradient discards it)
         return dx, dw, db, None
 
 
@@ -50,6 +63,7 @@ class Conv3x3Fn(Function):
     def forward(ctx, x, w, bias, act):
         y = ops.conv3x3_fwd(x, w, bias, act)
         ctx.act = act
+        ctx.has_bias = bias is not None
         ctx.save_for_backward(x, w, y if act != ACT_NONE else None)
         return y
 
@@ -59,7 +73,10 @@ class Conv3x3Fn(Function):
         x, w, y = ctx.saved_tensors
         dy = _c(dy)
         dx = ops.conv3x3_bwd_data(dy, w, y, ctx.act) if ctx.needs_input_grad[0] else None
-        dw, db = ops.conv3x3_bwd_weight(dy, x, y, ctx.act)
+        dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = ops.conv3x3_bwd_weight(dy, x, y, ctx.act, want_bias=ctx.has_bias and ctx.needs_input_grad[2])
+            dw, = _wanted(ctx, 1, (dw,))
         return dx, dw, db, None
 
 
@@ -78,7 +95,7 @@ class GroupNormFn(Function):
     def backward(ctx, dy):
         x, gamma, beta, mean, rstd = ctx.saved_tensors
         dx, dg, db = ops.groupnorm_bwd(_c(dy), x, gamma, beta, mean, rstd, ctx.groups, ctx.relu)
-        return dx, dg, db, None, None, None
+        return _wanted(ctx, 0, (dx, dg, db)) + (None, None, None)
 
 
 class Encoder2Fn(Function):
@@ -94,8 +111,8 @@ class Encoder2Fn(Function):
     @once_differentiable
     def backward(ctx, dz):
         x, w1, g1, b1, w2, g2, b2, stats = ctx.saved_tensors
-        dw1, dg1, db1, dw2, dg2, db2 = ops.encoder2_bwd(x, _c(dz), w1, g1, b1, w2, g2, b2, stats)
-        return None, dw1, dg1, db1, dw2, dg2, db2, None
+        grads = ops.encoder2_bwd(x, _c(dz), w1, g1, b1, w2, g2, b2, stats)
+        return (None,) + _wanted(ctx, 1, grads) + (None,)
 
 
 class ScalarCombineFn(Function):
@@ -188,7 +205,7 @@ class GateBlendFn(Function):
             dout = torch.zeros_like(residual)
         dout = _c(dout)
         dres, dgraw = ops.gate_blend_bwd(dout, _c(dgate), residual, gate_raw, ctx.min_gate)
-        return dout, dres, dgraw, None
+        return dout if ctx.needs_input_grad[0] else None, dres, dgraw, None
 
 
 class SpatialSmoothFn(Function):
@@ -243,28 +260,43 @@ class SpatialSmoothFn(Function):
             dg1 = ops.conv3x3_bwd_data(dgraw, w_g2, None, ACT_NONE, out_y=g1, out_act=ACT_RELU)
         else:
             dg1 = ops.conv3x3_bwd_data(dgraw, w_g2, gate_raw, ACT_SIGMOID)
-        dw_g2, db_g2 = ops.conv3x3_bwd_weight(dgraw, g1, y2, a2)
+        nig, hb = ctx.needs_input_grad, ctx.has_bias
+        # a frozen convolution skips its weight-gradient launch (and a frozen bias its store); the 1x1 heads' kernel always writes all four
+        wants = [(nig[1 + 2 * i], hb[i] and nig[2 + 2 * i]) for i in range(5)]      # (dW, db) of mb, a, b, g0, g2
+
+        def wgrad3(i, dy_, x_, y_, a_):
+            (ww, wb) = wants[i]
+            if not (ww or wb):
+                return None, None
+            dw_, db_ = ops.conv3x3_bwd_weight(dy_, x_, y_, a_, want_bias=wb)
+            return _wanted(ctx, 1 + 2 * i, (dw_,))[0], db_
+
+        dw_g2, db_g2 = wgrad3(4, dgraw, g1, y2, a2)
         a0, y0 = (ACT_NONE, None) if pre else (ACT_RELU, g1)
         # residual: blend term + gate-net term in one store; d(smoothed) - d(residual) (residual = x - smoothed) as the second output
         dres_tot, d_tot = ops.conv3x3_bwd_data(dg1, w_g0, y0, a0, add=dres, sub_from=dout)
-        dw_g0, db_g0 = ops.conv3x3_bwd_weight(dg1, res, y0, a0)
+        dw_g0, db_g0 = wgrad3(3, dg1, res, y0, a0)
         pre_f = pre and ctx.fused_heads
         if ctx.fused_heads:
             dx, dfeat, dw_a, db_a, dw_b, db_b = ops.smooth_heads_bwd(d_tot, x, feat, w_a, b_a, w_b, b_b, dil, dx_add=dres_tot, dfeat_relu=pre_f)
         else:
             dx, da, db = ops.edge_smooth_bwd(d_tot, x, a_soft, b_soft, rank, dil, dx_add=dres_tot)
             dfeat = ops.conv1x1_bwd_data(db, w_b, None, ACT_NONE, add=ops.conv1x1_bwd_data(da, w_a, None, ACT_NONE))
-            dw_a, db_a = ops.conv1x1_bwd_weight(da, feat, None, ACT_NONE, want_bias=ctx.has_bias[1])
-            dw_b, db_b = ops.conv1x1_bwd_weight(db, feat, None, ACT_NONE, want_bias=ctx.has_bias[2])
+            dw_a = dw_b = db_a = db_b = None
+            if any(wants[1]):
+                dw_a, db_a = ops.conv1x1_bwd_weight(da, feat, None, ACT_NONE, want_bias=wants[1][1])
+            if any(wants[2]):
+                dw_b, db_b = ops.conv1x1_bwd_weight(db, feat, None, ACT_NONE, want_bias=wants[2][1])
         af, yf = (ACT_NONE, None) if pre_f else (ACT_RELU, feat)
-        dw_mb, db_mb = ops.conv3x3_bwd_weight(dfeat, g, yf, af)
+        dw_mb, db_mb = wgrad3(0, dfeat, g, yf, af)
         if ctx.needs_input_grad[0]:
             dx = ops.sobel_bwd(ops.conv3x3_bwd_data(dfeat, w_mb, yf, af), add=dx)
         else:
             dx = None
-        hb = ctx.has_bias
-        return (dx, dw_mb, db_mb if hb[0] else None, dw_a.reshape(w_a.shape), db_a if hb[1] else None, dw_b.reshape(w_b.shape),
-                db_b if hb[2] else None, dw_g0, db_g0 if hb[3] else None, dw_g2, db_g2 if hb[4] else None, None, None, None)
+        heads = _wanted(ctx, 3, (None if dw_a is None else dw_a.reshape(w_a.shape), db_a if hb[1] else None,
+                                 None if dw_b is None else dw_b.reshape(w_b.shape), db_b if hb[2] else None))
+        return (dx, dw_mb, db_mb if hb[0] else None) + heads + (dw_g0, db_g0 if hb[3] else None, dw_g2, db_g2 if hb[4] else None,
+                                                                None, None, None)
 
 
 class TcnBlockFn(Function):
@@ -288,8 +320,8 @@ class TcnBlockFn(Function):
         g = ops.tcn_block_bwd(x, _c(dy), conv_w, conv_b, gn_w, gn_b, gate_w, gate_b, pw, proj_b, dilation, groups, eps,
                               drop_mask=ctx.drop_mask, want_dx=ctx.needs_input_grad[0])
         dpw = g["proj_w"].reshape(proj_w.shape) if proj_w is not None else None
-        return (g["dx"] if ctx.needs_input_grad[0] else None, g["conv_w"], g["conv_b"], g["gn_w"], g["gn_b"], g["gate_w"],
-                g["gate_b"], dpw, g.get("proj_b"), None, None, None, None)
+        return (g["dx"] if ctx.needs_input_grad[0] else None,) + _wanted(ctx, 1, (g["conv_w"], g["conv_b"], g["gn_w"], g["gn_b"], g["gate_w"],
+                                                                                g["gate_b"], dpw, g.get("proj_b"))) + (None, None, None, None)
 
 
 class TcnChainHeadFn(Function):
@@ -313,7 +345,10 @@ class TcnChainHeadFn(Function):
         groups, eps = ctx.cfg
         dh = _c(dh)
         w2 = head_w.reshape(head_w.shape[0], head_w.shape[1])
-        dw_h, db_h = ops.conv1x1_bwd_weight(dh, y3, None, ACT_NONE, want_bias=True)
+        dw_h = db_h = None
+        if ctx.needs_input_grad[19] or ctx.needs_input_grad[20]:
+            dw_h, db_h = ops.conv1x1_bwd_weight(dh, y3, None, ACT_NONE, want_bias=ctx.needs_input_grad[20])
+            dw_h, = _wanted(ctx, 19, (dw_h.reshape(head_w.shape),))
         # the head's backward-data rides inside the last block's backward kernel where that kernel applies (dy = dh W_h never reaches HBM)
         head_in_kernel = groups == 8 and ops.tcn_block_bwd_head_supported(y2, dh, w2, 4)
         dy = None if head_in_kernel else ops.conv1x1_bwd_data(dh, w2, None, ACT_NONE)
@@ -326,7 +361,7 @@ class TcnChainHeadFn(Function):
                 g = ops.tcn_block_bwd(xin, dy, cw, cb, gw, gb, tw, tb, None, None, dil, groups, eps, want_dx=(i > 0 or ctx.needs_input_grad[0]))
             grads[6 * i:6 * i + 6] = [g["conv_w"], g["conv_b"], g["gn_w"], g["gn_b"], g["gate_w"], g["gate_b"]]
             dy = g["dx"]
-        return (dy if ctx.needs_input_grad[0] else None,) + tuple(grads) + (dw_h.reshape(head_w.shape), db_h, None, None)
+        return (dy if ctx.needs_input_grad[0] else None,) + _wanted(ctx, 1, grads) + (dw_h, db_h, None, None)
 
 
 class FilmFn(Function):
@@ -360,7 +395,7 @@ class FilmFusedFn(Function):
     def backward(ctx, dz, _dg, _db):
         h, z_type, *params = ctx.saved_tensors
         dh, grads = ops.film_fused_bwd(z_type, h, _c(dz), params)
-        return (dh if ctx.needs_input_grad[0] else None, None) + tuple(grads)
+        return (dh if ctx.needs_input_grad[0] else None, None) + _wanted(ctx, 2, grads)
 
 
 class ChannelScaleFn(Function):
@@ -397,11 +432,11 @@ class VQFn(Function):
         n = z.numel() // d
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(z, codebook, idx, counts, zq)
-        ctx.mark_non_differentiable(idx, counts)
-        # stats = {sum ||z - z_q||^2, perplexity, rows re-evaluated, mean squared error}: the two loss terms are numerically equal
-        mse = stats.narrow(0, 3, 1).reshape(())
-        ctx.mark_non_differentiable(stats)
-        return zq, mse, mse.clone(), stats.narrow(0, 1, 1).reshape(()), idx, counts, stats
+        # stats = {sum ||z - z_q||^2, perplexity, rows re-evaluated, mean squared error}: the two loss terms are numerically equal; the three
+        # differentiable outputs are views of one copy (the single launch the two loss terms cost before), not of the non-differentiable stats
+        st = stats.clone()
+        ctx.mark_non_differentiable(idx, counts, stats)
+        return zq, st[3], st.narrow(0, 3, 1).reshape(()), st[1], idx, counts, stats
 
     @staticmethod
     @once_differentiable
@@ -455,7 +490,7 @@ class DecoderMseFn(Function):
         if g is None:
             return (None,) * 8
         dz, dw1, db1, dw2, db2 = ops.decoder_mse_bwd(z, w1, b1, w2, b2, target, mask, g.reshape(1).float().contiguous(), stats)
-        return dz, dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2, None, None, None
+        return _wanted(ctx, 0, (dz, dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2)) + (None, None, None)
 
 
 def decoder_mse(z, w1, b1, w2, b2, target, mask=None, want_xhat=False):

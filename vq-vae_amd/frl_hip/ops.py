@@ -194,45 +194,57 @@ def _f32(t: Optional[torch.Tensor], name: str):
     return t
 
 
-_DEFER = {"on": False, "keep": []}
+_DEFER = {"on": False, "keep": [], "dest": {}, "drop": set()}
 
 
 class deferred_reductions:
     """`with deferred_reductions(params): loss.backward()` -- the slab reductions behind the weight-gradient kernels of the backward pass
     (csrc/defer.hip, include/frl_hip.h) are parked and run in ONE launch when the block ends, on the current stream.  While it is open every
-    kernel call gets a workspace of its own (the parked slabs live in them), kept until the flush.  Before the flush the block checks that
-    every parked destination lies inside the .grad of one of `params`: autograd must have adopted the tensors the kernels' wrappers
-    returned, not copies of them (a parameter used twice, or a hook that clones gradients, would read a tensor nothing has written yet)."""
+    kernel call gets a workspace of its own (the parked slabs live in them), kept until the flush, and the storage of every gradient tensor
+    the kernel wrappers allocate (`grad_empty`) is held until the flush as well, so that no parked destination can be freed and its address
+    handed to another tensor.  Before the flush the block checks that every parked destination lies inside one of those held gradients,
+    and that the gradient either was handed to `discard` (a gradient autograd drops: a frozen parameter) or is the .grad of one of `params`:
+    autograd must have adopted the tensors the kernels' wrappers returned, not copies of them (a parameter used twice, a gradient
+    accumulated into an existing .grad, or a hook that clones gradients, would read a tensor nothing has written yet).  When the check
+    fails, autograd has already summed or copied the unwritten gradient: the .grad of the parameters involved is invalid and must be zeroed
+    (or set to None) before the backward is repeated without deferral.  The held gradients are marked as used on the current stream, so
+    that one allocated on a side stream is not reused before the flush has written it."""
 
     def __init__(self, params):
         self.params = list(params)
 
     def __enter__(self):
         check(_lib.load().frl_defer_begin(), "frl_defer_begin")
-        _DEFER["keep"] = []
-        _DEFER["on"] = True
+        _DEFER.update(keep=[], dest={}, drop=set(), on=True)
         return self
 
     def __exit__(self, et, ev, tb):
         lib = _lib.load()
         _DEFER["on"] = False
-        keep, _DEFER["keep"] = _DEFER["keep"], []
+        keep, dest, drop = _DEFER["keep"], _DEFER["dest"], _DEFER["drop"]
+        _DEFER.update(keep=[], dest={}, drop=set())
         if et is not None:
             lib.frl_defer_abort()
             return False
         try:
+            import bisect
             buf = (ctypes.c_void_p * 512)()
             n = lib.frl_defer_destinations(ctypes.cast(buf, ctypes.c_void_p), 512)
+            held = sorted((a, a + s.nbytes()) for a, s in dest.items())
             spans = sorted((g.data_ptr(), g.data_ptr() + g.numel() * g.element_size())
                            for g in (p.grad for p in self.params) if g is not None)
-            starts = [a for a, _ in spans]
-            import bisect
             for i in range(n):
                 d = int(buf[i])
-                k = bisect.bisect_right(starts, d) - 1
+                k = bisect.bisect_right(held, (d, float("inf"))) - 1
+                if k < 0 or not (held[k][0] <= d < held[k][1]):
+                    raise RuntimeError("deferred_reductions: a parked gradient was not allocated by the kernel wrappers inside this block")
+                if held[k][0] in drop:
+                    continue
+                k = bisect.bisect_right(spans, (d, float("inf"))) - 1
                 if k < 0 or not (spans[k][0] <= d < spans[k][1]):
                     raise RuntimeError("deferred_reductions: a parked gradient is not the .grad of any parameter (autograd copied or summed "
-                                       "it: a parameter used twice, or a gradient hook); run this backward without deferral")
+                                       "it: a parameter used twice, a gradient accumulated into an existing .grad, or a gradient hook); "
+                                       "the .grad of the parameters involved is now invalid: zero it, then run this backward without deferral")
         except Exception:
             lib.frl_defer_abort()
             raise
@@ -242,7 +254,30 @@ class deferred_reductions:
         cur = torch.cuda.current_stream()
         for t in keep:                                          # slabs written on a side stream, read by the flush on this one
             t.record_stream(cur)
+        for st in dest.values():                                # gradients written by the flush: not reused before it has run
+            torch.empty(0, dtype=torch.uint8, device=cur.device).set_(st).record_stream(cur)
         return False
+
+
+def grad_empty(shape, device) -> torch.Tensor:
+    """A float32 parameter-gradient tensor for a weight-gradient kernel to fill.  Inside `deferred_reductions` its STORAGE is held until the
+    flush (not the tensor: an extra reference to the tensor would make autograd clone it instead of adopting it as the .grad)."""
+    g = torch.empty(shape, dtype=torch.float32, device=device)
+    if _DEFER["on"]:
+        st = g.untyped_storage()
+        _DEFER["dest"][st.data_ptr()] = st
+    return g
+
+
+def discard(*grads) -> None:
+    """Gradients a kernel computed that autograd will not receive (the parameter is frozen, and the kernel has no way to skip them): inside
+    `deferred_reductions` their parked reductions still write them at the flush; they stay held and are exempt from the .grad check.  Only
+    gradients that `grad_empty` allocated in this block are exempted (both are alive, so an equal address is the same storage); others
+    are never parked and need nothing."""
+    if _DEFER["on"]:
+        for g in grads:
+            if g is not None and g.untyped_storage().data_ptr() in _DEFER["dest"]:
+                _DEFER["drop"].add(g.untyped_storage().data_ptr())
 
 
 def workspace(nbytes: int, device) -> torch.Tensor:
@@ -306,8 +341,8 @@ def _conv1x1_bwd_weight_impl(dy: torch.Tensor, x: torch.Tensor, y: Optional[torc
     lib = _lib.load()
     nbytes = lib.frl_conv1x1_bwd_weight_workspace_bytes(p, cin, cout)
     ws = workspace(nbytes, dy.device)
-    dw = torch.empty(cout, cin, dtype=torch.float32, device=dy.device)
-    db = torch.empty(cout, dtype=torch.float32, device=dy.device) if want_bias else None
+    dw = grad_empty((cout, cin), dy.device)
+    db = grad_empty((cout,), dy.device) if want_bias else None
     check(lib.frl_conv_tap_bwd_weight(_p(dy), _p(y), act, _p(x), _p(dw), cin, 1, _p(db), p, cin, cout, 1, 1, 0,
                                       _dt(dy), _p(ws), ws.numel(), 1 if scalar_frags else 0, _stream()),
           "frl_conv_tap_bwd_weight")
@@ -370,7 +405,7 @@ def vq_bwd(g_out: Optional[torch.Tensor], z: torch.Tensor, codebook: torch.Tenso
     lib = _lib.load()
     ws = workspace(lib.frl_vq_workspace_bytes(n, k, d), z.device)
     gz = torch.empty_like(z) if want_gz else None
-    ge = torch.empty(k, d, dtype=torch.float32, device=z.device) if want_ge else None
+    ge = grad_empty((k, d), z.device) if want_ge else None
     sums = torch.empty(k, d, dtype=torch.float32, device=z.device) if want_sums else None
     cb32 = _f32(codebook, "codebook")
     if _DEFER["on"]:                                            # the parked codebook-gradient reduction reads these when the flush runs
@@ -457,10 +492,7 @@ def encoder2_bwd(x, dz, w1, g1, b1, w2, g2, b2, stats):
     b, c = x.shape[0], x.shape[-1]
     hw = x.numel() // (b * c)
     lib = _lib.load()
-    dw1 = torch.empty(w1.shape, dtype=torch.float32, device=x.device)
-    dw2 = torch.empty(w2.shape, dtype=torch.float32, device=x.device)
-    dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
-    dg2, db2 = torch.empty_like(g2), torch.empty_like(b2)
+    dw1, dg1, db1, dw2, dg2, db2 = (grad_empty(t.shape, x.device) for t in (w1, g1, b1, w2, g2, b2))
     ws = workspace(lib.frl_encoder2_workspace_bytes(b), x.device)
     check(lib.frl_encoder2_bwd(_p(x), _p(dz), _p(_f32(w1, "w1")), _p(g1), _p(b1), _p(_f32(w2, "w2")), _p(g2), _p(b2), _p(stats), _p(dw1), _p(dg1),
                                _p(db1), _p(dw2), _p(dg2), _p(db2), b, hw, _p(ws), ws.numel(), _stream()), "frl_encoder2_bwd")
@@ -585,7 +617,7 @@ def film_fused_bwd(z_type: torch.Tensor, h: torch.Tensor, dz: torch.Tensor, para
     lib = _lib.load()
     ws = workspace(lib.frl_film_fused_workspace_bytes(), h.device)
     dh = torch.empty_like(h)
-    grads = [torch.empty(p.shape, dtype=torch.float32, device=h.device) for p in params]
+    grads = [grad_empty(p.shape, h.device) for p in params]
     check(lib.frl_film_fused_bwd(_p(z_type), _p(h), _p(dz), *_film_params(params), _p(dh), *[_p(g) for g in grads], b, t, hw, _p(ws), ws.numel(),
                                  _stream()), "frl_film_fused_bwd")
     return dh, grads
@@ -799,13 +831,13 @@ def conv3x3_bwd_data(dy, w, y=None, act: int = ACT_NONE, add=None, sub_from=None
 
 
 @_timed("conv3x3_bwd_weight")
-def conv3x3_bwd_weight(dy, x, y=None, act: int = ACT_NONE, scalar_frags: bool = False):
+def conv3x3_bwd_weight(dy, x, y=None, act: int = ACT_NONE, scalar_frags: bool = False, want_bias: bool = True):
     b, h, wd, cout = dy.shape
     cin = x.shape[-1]
     lib = _lib.load()
     ws = workspace(lib.frl_conv3x3_bwd_weight_workspace_bytes(b, h, wd, cin, cout), dy.device)
-    dw = torch.empty(cout, cin, 3, 3, dtype=torch.float32, device=dy.device)
-    db = torch.empty(cout, dtype=torch.float32, device=dy.device)
+    dw = grad_empty((cout, cin, 3, 3), dy.device)
+    db = grad_empty((cout,), dy.device) if want_bias else None
     check(lib.frl_conv3x3_bwd_weight(_p(dy), _p(y), act, _p(x), _p(dw), _p(db), b, h, wd, cin, cout, _dt(dy), _p(ws),
                                      ws.numel(), 1 if scalar_frags else 0, _stream()), "frl_conv3x3_bwd_weight")
     return dw, db
@@ -903,8 +935,7 @@ def smooth_heads_bwd(d_smoothed, x, feat, wa, ba, wb, bb, coarse_dilation: int, 
     ws = workspace(lib.frl_smooth_heads_workspace_bytes(npix), x.device)
     scratch = torch.empty(lib.frl_smooth_heads_bwd_scratch_bytes(npix), dtype=torch.uint8, device=x.device)
     dx, dfeat = torch.empty_like(x), torch.empty_like(feat)
-    dwa, dwb = torch.empty(wa.shape, dtype=torch.float32, device=x.device), torch.empty(wb.shape, dtype=torch.float32, device=x.device)
-    dba, dbb = torch.empty_like(ba), torch.empty_like(bb)
+    dwa, dba, dwb, dbb = (grad_empty(t.shape, x.device) for t in (wa, ba, wb, bb))
     check(lib.frl_smooth_heads_bwd_masked(_p(d_smoothed), _p(x), _p(feat), _p(_f32(wa, "wa")), _p(_f32(ba, "ba")), _p(_f32(wb, "wb")),
                                           _p(_f32(bb, "bb")), _p(dx_add), _p(dx), _p(dfeat), _p(dwa), _p(dba), _p(dwb), _p(dbb), _p(scratch),
                                           scratch.numel(), b, h, w, coarse_dilation, int(dfeat_relu), _p(ws), ws.numel(), _stream()),
@@ -1012,7 +1043,7 @@ def tcn_block_bwd_head(x, dh, head_w, conv_w, conv_b, gn_w, gn_b, gate_w, gate_b
     _chk_rows(dh, ch, "tcn_block_bwd_head.dh")
     lib = _lib.load()
     dx = torch.empty_like(x)
-    g = {k: torch.empty_like(v, dtype=torch.float32) for k, v in
+    g = {k: grad_empty(v.shape, x.device) for k, v in
          dict(conv_w=conv_w, conv_b=conv_b, gn_w=gn_w, gn_b=gn_b, gate_w=gate_w, gate_b=gate_b).items()}
     ws = workspace(lib.frl_tcn_hot_bwd_head_workspace_bytes(npix), x.device)
     with span("tcn_block_bwd.main"):
@@ -1039,7 +1070,7 @@ def tcn_block_bwd(x, dy, conv_w, conv_b, gn_w, gn_b, gate_w, gate_b, proj_w, pro
     if hot:
         skip_dx = (not want_dx) and drop_mask is None and bool(lib.frl_tcn_hot_bwd_nodx_supported(npix, hw))
         dx = None if skip_dx else torch.empty_like(x)
-        g = {k: torch.empty_like(v, dtype=torch.float32) for k, v in
+        g = {k: grad_empty(v.shape, x.device) for k, v in
              dict(conv_w=conv_w, conv_b=conv_b, gn_w=gn_w, gn_b=gn_b, gate_w=gate_w, gate_b=gate_b).items()}
         ws = workspace(lib.frl_tcn_hot_bwd_workspace_bytes(npix), dev)
         with span("tcn_block_bwd.main"):
@@ -1050,7 +1081,7 @@ def tcn_block_bwd(x, dy, conv_w, conv_b, gn_w, gn_b, gate_w, gate_b, proj_w, pro
         return g
     if allow_fused and lib.frl_tcn_block_bwd_fused_supported(t, cin, cout, groups, int(proj_w is not None), _dt(x)):
         dx = torch.empty_like(x)
-        g = {k: torch.empty_like(v, dtype=torch.float32) for k, v in
+        g = {k: grad_empty(v.shape, x.device) for k, v in
              dict(conv_w=conv_w, conv_b=conv_b, gn_w=gn_w, gn_b=gn_b, gate_w=gate_w, gate_b=gate_b).items()}
         ws = workspace(lib.frl_tcn_block_bwd_fused_workspace_bytes(npix), dev)
         with span("tcn_block_bwd.main"):
@@ -1063,8 +1094,7 @@ def tcn_block_bwd(x, dy, conv_w, conv_b, gn_w, gn_b, gate_w, gate_b, proj_w, pro
     oshape = x.shape[:-1] + (cout,)
     dconv = torch.empty(oshape, dtype=x.dtype, device=dev)
     dgpre, normed, dres = torch.empty_like(dconv), torch.empty_like(dconv), torch.empty_like(dconv)
-    dgam = torch.empty(cout, dtype=torch.float32, device=dev)
-    dbet = torch.empty(cout, dtype=torch.float32, device=dev)
+    dgam, dbet = grad_empty((cout,), dev), grad_empty((cout,), dev)
     gate_w2 = gate_w.reshape(cout, cout)
     ws = workspace(lib.frl_tcn_block_bwd_workspace_bytes(npix, cout), dev)
     with span("tcn_block_bwd.main"):
@@ -1076,8 +1106,7 @@ def tcn_block_bwd(x, dy, conv_w, conv_b, gn_w, gn_b, gate_w, gate_b, proj_w, pro
     check(lib.frl_tcn_block_bwd_data(_p(dconv), _p(dres), _p(conv_w), _p(proj_w), _p(dx), npix, hw, t, cin, cout, dilation,
                                      _dt(x), _p(ws1), ws1.numel(), _stream()), "frl_tcn_block_bwd_data")
     p = b * t * hw
-    dw = torch.empty(cout, cin, 3, dtype=torch.float32, device=dev)
-    dcb = torch.empty(cout, dtype=torch.float32, device=dev)
+    dw, dcb = grad_empty((cout, cin, 3), dev), grad_empty((cout,), dev)
     ws2 = workspace(lib.frl_conv1x1_bwd_weight_workspace_bytes(p, max(cin, cout), cout), dev)
     for k in range(3):
         check(lib.frl_conv_tap_bwd_weight(_p(dconv), None, 0, _p(x), ctypes.c_void_p(dw.data_ptr() + 4 * k), cin * 3, 3,
@@ -1119,8 +1148,7 @@ def decoder_mse_bwd(z, w1, b1, w2, b2, target, mask, gscale, stats):
     lib = _lib.load()
     ws = workspace(lib.frl_decoder_mse_workspace_bytes(p, cz), z.device)
     dz = torch.empty_like(z)
-    dw1, db1 = torch.empty_like(w1, dtype=torch.float32), torch.empty_like(b1, dtype=torch.float32)
-    dw2, db2 = torch.empty_like(w2, dtype=torch.float32), torch.empty_like(b2, dtype=torch.float32)
+    dw1, db1, dw2, db2 = (grad_empty(t.shape, z.device) for t in (w1, b1, w2, b2))
     check(lib.frl_decoder_mse_bwd(_p(z), _p(w1), _p(b1), _p(w2), _p(b2), _p(target), _p(mask), _p(gscale), _p(stats), _p(dz), _p(dw1),
                                   _p(db1), _p(dw2), _p(db2), p, cz, _p(ws), ws.numel(), _stream()), "frl_decoder_mse_bwd")
     return dz, dw1, db1, dw2, db2
