@@ -138,6 +138,11 @@ int frl_scalar_combine_dev(const float* const* terms_host, const float* coef_hos
 int frl_scalar_combine_aux(const float* const* terms_host, const float* coef_host, const float* const* mult_host, const float* aux_coef_host,
                            int n, float* out, float* ok_out, float* aux_out, frl_stream_t stream);
 int frl_scalar_fanout_dev(const float* g, const float* coef_host, const float* const* mult_host, int n, float* out, frl_stream_t stream);
+/* frl_scalar_fanout_dev plus the check of a promise: promise_host (n device pointers, entries or the array may be NULL) names, per term, the
+ * gradient the term was promised at forward time (frl_decoder_mse_fwd_bwd computed its gradients with it); flag[0] (device int) is set to 1
+ * when a term's gradient differs from its promise and is left alone otherwise -- a sticky word the host polls where it synchronises anyway. */
+int frl_scalar_fanout_guard(const float* g, const float* coef_host, const float* const* mult_host, const float* const* promise_host, int n,
+                            float* out, int* flag, frl_stream_t stream);
 
 /* ---- fused two-layer type encoder (csrc/enc_fused.hip) -----------------------------------------------------------
  * conv1x1 C0->C1 (no bias) -> GroupNorm(G1) -> ReLU -> conv1x1 C1->C2 (no bias) -> GroupNorm(G2): Conv2DEncoder with two layers
@@ -380,6 +385,20 @@ int frl_decoder_mse_fwd(const void* z, const float* w1, const float* b1, const f
 int frl_decoder_mse_bwd(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* target,
                         const uint8_t* mask, const float* gscale, const float* stats, void* dz, float* dw1, float* db1,
                         float* dw2, float* db2, int64_t P, int Cz, void* ws, size_t ws_bytes, frl_stream_t stream);
+/* Train step: loss AND gradients from ONE pass over (z, target).  The backward kernel recomputes all the forward computes, so when the
+ * gradient the loss will receive is known before the forward runs (gscale: device scalar, null = 1; the loss enters the total with a fixed
+ * coefficient and the total is differentiated with upstream 1) it also accumulates the loss: no forward kernel, one pass over the data less.
+ * out = {loss, n_valid} and dz are what frl_decoder_mse_fwd / frl_decoder_mse_bwd write (dz and the weight gradients bit for bit).  The
+ * weight-gradient slabs stay unreduced in `buf` (frl_decoder_mse_onepass_bytes; the caller's own, untouched until the reduction has run)
+ * and *nslab receives their number; frl_decoder_mse_reduce turns them into dw1 [128][Cz], db1 [128], dw2 [64][128], db2 [64] -- parked
+ * when a deferral is open (csrc/defer.hip), a launch of its own otherwise.  ctl: 4 zeroed 32-bit device words that no concurrent call
+ * shares (used by the mask count); every call leaves them zero.  With a mask, n_valid comes from a count over the mask bytes (one small
+ * launch in front of the pass); the loss record is written by the small finalize launch behind it. */
+size_t frl_decoder_mse_onepass_bytes(int64_t P, int Cz);
+int frl_decoder_mse_fwd_bwd(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* target,
+                            const uint8_t* mask, const float* gscale, float* out, void* dz, void* buf, size_t buf_bytes, void* ctl,
+                            int* nslab, int64_t P, int Cz, frl_stream_t stream);
+int frl_decoder_mse_reduce(const void* buf, int nslab, float* dw1, float* db1, float* dw2, float* db2, int Cz, frl_stream_t stream);
 int frl_decoder_mse_bwd_subgroups(int on);   /* A/B hook: 1 (default) = two independent 4-wave subgroups per workgroup, 0 = lockstep workgroups; returns the previous setting */
 
 /* ---- vector quantizer ------------------------------------------------------------------------------------------

@@ -7,6 +7,8 @@
 // ~0.9 GB for them on the phase path at cfg2); xhat is written only when the caller asks for it.
 // Backward: recomputes the chain per pixel in registers, produces dz, and contracts the weight gradients over pixels inside
 // the kernel (LDS tiles + ds_read_b64_tr_b16 fragments; every wave owns a block-row of dW2 / dW1), as tcn_fused.hip does.
+// One pass (train step): the backward recomputes everything the forward computes, so when the upstream gradient of the loss is known
+// before the forward runs (frl_decoder_mse_fwd_bwd) the backward kernel also accumulates the loss and no forward kernel is launched.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
 #include "frl_pack.hpp"
@@ -167,12 +169,26 @@ __device__ __forceinline__ void df_sg_sync(unsigned* bar, unsigned& gen, int lan
 // NW waves per workgroup (SG = false) or per SUBGROUP (SG = true: the workgroup is two independent 4-wave subgroups, one wave of each per
 // SIMD, each with its own 64-row tiles, rounds, barriers and slab -- the two waves of a SIMD then sit in different phases of the round
 // instead of both waiting at the same barrier); tile = 16*NW rows.  slab (floats): dW2 [64][128] | dW1 [128][CZP] | db2 [64] | db1 [128]
-template <int NFZ, int NW, bool SG = false>
+//
+// LOSS: the kernel also accumulates the masked sum of diff^2 and the valid count (float per lane, double per wave and workgroup, as
+// dec_mse_fwd_kernel does) and leaves them in la.partial for dec_mse_finalize_kernel.  (A fold by the last workgroup to arrive, behind a
+// release fence and a ticket as in vq_assign_resident_kernel, was measured and dropped: it lengthened the <2,4> kernel by 9 us at 262 k
+// rows and the subgroup kernel by 2..7 us at 1.3 M rows, run-to-run noise included; the finalize launch it would replace costs 5.)
+// n_valid must be known before the pass: la.nv_host (no mask: P * 64) or la.out[1] (dec_mask_count_kernel).
+template <bool LOSS> struct DecLoss {};
+template <> struct DecLoss<true> {
+  double* partial;      // [gridDim.x][2]
+  const float* out;     // {loss, n_valid} record: only n_valid is read
+  float* out_w;         // (host side: the record dec_mse_finalize_kernel writes behind the pass)
+  float nv_host;        // n_valid when the host knows it, else < 0: read from out[1]
+};
+
+template <int NFZ, int NW, bool SG = false, bool LOSS = false>
 __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const TT* __restrict__ Z, const frag8* __restrict__ Wpk, const float* __restrict__ b1,
                                                                const float* __restrict__ b2, const TT* __restrict__ TGT,
                                                                const uint8_t* __restrict__ mask, const float* __restrict__ gscale,
                                                                const float* __restrict__ stats, TT* __restrict__ DZ, int64_t P, int Cz,
-                                                               float* __restrict__ slab) {
+                                                               float* __restrict__ slab, const DecLoss<LOSS> la) {
   constexpr int CZP = 32 * NFZ, CB = CZP / 16, R = 16 * NW, NTH = SG ? 512 : 64 * NW;
   constexpr int PX = DF_F + 8, PH = DF_H + 8, PZ = CZP + 8;            // LDS tile pitches (16-byte skew)
   static_assert(!SG || NW == 4, "subgroups are four waves");
@@ -203,7 +219,11 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
   const float* b1q = tb + 32 * kc;
   const float* b2q = tb + 128 + 16 * kc;
   const bool fastz = (Cz == CZP);
-  const float nv = stats[1];
+  float nv;
+  if constexpr (LOSS) nv = la.nv_host >= 0.f ? la.nv_host : la.out[1]; else nv = stats[1];
+  float sq = 0.f;
+  int nrow = 0;                                                // valid rows of this wave (wave-uniform: a scalar register)
+  (void)sq; (void)nrow;
   const float ksc = nv > 0.f ? (gscale ? gscale[0] : 1.f) * 2.f / nv : 0.f;
 
   // weight-gradient ownership
@@ -261,6 +281,13 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
     dec_chain<NFZ>(h, xh, zt, w1, w2, b1q, b2q, ht, lane);
     LQTile<TT, 2> dxt;
     const float kv = valid ? ksc : 0.f;
+    if constexpr (LOSS) {
+      if (valid) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) { const float d = xh[j] - (float)tt.f[j >> 3][j & 7]; sq = fmaf(d, d, sq); }
+      }
+      nrow += __popcll(__ballot(valid));                        // (each lane of a valid row holds 16 of its 64 elements)
+    }
 #pragma unroll
     for (int j = 0; j < 16; ++j) dxt.f[j >> 3][j & 7] = (bf16)(kv * (xh[j] - (float)tt.f[j >> 3][j & 7]));
     f32x4 dhacc[8];
@@ -352,6 +379,59 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
 #pragma unroll
     for (int r = 0; r < 4; ++r) my[DF_F * DF_H + DF_H * CZP + w2row * 16 + kc * 4 + r] = ab2[r];
   }
+  if constexpr (LOSS) {
+    constexpr int NWV = NTH / 64;
+    __shared__ double lred[2 * NWV];
+    const double sd = wave_sum_d((double)sq), cd = 16.0 * (double)nrow;
+    if (lane == 0) { lred[tid >> 6] = sd; lred[NWV + (tid >> 6)] = cd; }
+    __syncthreads();
+    if (tid == 0) {
+      double s = lred[0], c = lred[NWV];
+#pragma unroll
+      for (int w = 1; w < NWV; ++w) { s += lred[w]; c += lred[NWV + w]; }              // fixed order
+      la.partial[2 * blockIdx.x + 0] = s;
+      la.partial[2 * blockIdx.x + 1] = c;
+    }
+  }
+}
+
+// Valid-element count of a masked one-pass call, from the mask bytes alone: out[1] = 64 * (non-zero bytes), the value dec_mse_fwd_kernel's
+// count comes to.  Integer atomics (order-independent); the last workgroup writes the record and leaves ctl {ticket, -, count} zero.
+__global__ __launch_bounds__(256) void dec_mask_count_kernel(const uint8_t* __restrict__ mask, int64_t P, unsigned* __restrict__ ctl,
+                                                             float* __restrict__ out) {
+  __shared__ unsigned wg_n;
+  const int tid = threadIdx.x;
+  if (tid == 0) wg_n = 0u;
+  __syncthreads();
+  const int64_t gtid = (int64_t)blockIdx.x * 256 + tid, gstep = (int64_t)gridDim.x * 256;
+  const int64_t n16 = ((reinterpret_cast<uintptr_t>(mask) & 15) == 0) ? (P >> 4) : 0;
+  unsigned n = 0;
+  const uint4* m16 = reinterpret_cast<const uint4*>(mask);
+  for (int64_t i = gtid; i < n16; i += gstep) {
+    const uint4 v = m16[i];
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)                                // one bit per non-zero byte
+      n += __popc((w[k] | ((w[k] & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u);
+  }
+  for (int64_t i = n16 * 16 + gtid; i < P; i += gstep) n += mask[i] != 0 ? 1u : 0u;
+  if (n) atomicAdd(&wg_n, n);
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long* total = reinterpret_cast<unsigned long long*>(ctl + 2);
+    if (wg_n) __hip_atomic_fetch_add(total, (unsigned long long)wg_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned ticket = __hip_atomic_fetch_add(ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket == gridDim.x - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned long long t = __hip_atomic_load(total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out[1] = (float)((double)t * (double)DF_F);
+      __hip_atomic_store(total, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ctl, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 template <int NFZ>
@@ -397,29 +477,35 @@ static const frag8* dec_packed(const float* w1, const float* w2, int Cz, int bwd
 static unsigned df_fwd_grid(int64_t P) { int64_t g = ((P + 15) / 16 + 3) / 4; if (g > DF_GRID_MAX) g = DF_GRID_MAX; return (unsigned)(g < 1 ? 1 : g); }
 static unsigned df_bwd_grid(int64_t P, int R) { int64_t g = (P + R - 1) / R; if (g > 256) g = 256; return (unsigned)(g < 1 ? 1 : g); }
 
-template <int NFZ, int NW>
+// LOSS (one pass): the slabs are left unreduced in `ws` (frl_decoder_mse_reduce), *nslab_out receives their number
+template <int NFZ, int NW, bool LOSS = false>
 static int launch_dec_bwd(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* tgt,
                           const uint8_t* mask, const float* gscale, const float* stats, void* dz, float* dw1, float* db1, float* dw2,
-                          float* db2, int64_t P, int Cz, char* ws, hipStream_t st) {
+                          float* db2, int64_t P, int Cz, char* ws, hipStream_t st, DecLoss<LOSS> la = DecLoss<LOSS>{}, int* nslab_out = nullptr) {
   constexpr int CZP = 32 * NFZ, CB = CZP / 16, R = 16 * NW;
   const unsigned grid = df_bwd_grid(P, R);
   const size_t slab_n = (size_t)DF_F * DF_H + DF_H * CZP + DF_F + DF_H;
   const frag8* pk = dec_packed<NFZ>(w1, w2, Cz, 1, reinterpret_cast<frag8*>(ws + ((grid * slab_n * sizeof(float) + 255) / 256) * 256), st);
   const size_t lds = (size_t)(8 * NFZ + 16 + 16 + CB * 4) * 64 * sizeof(frag8) + 192 * sizeof(float) +
                      (size_t)R * ((DF_F + 8) + 2 * (DF_H + 8) + (CZP + 8)) * sizeof(TT);
-  auto kern = dec_mse_bwd_kernel<NFZ, NW>;
+  auto kern = dec_mse_bwd_kernel<NFZ, NW, false, LOSS>;
   FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  FRL_LAUNCH_AS("dec_mse_bwd_kernel", kern, dim3(grid), dim3(64 * NW), lds, st, (const TT*)z, (const frag8*)pk, b1, b2, (const TT*)tgt, mask, gscale, stats, (TT*)dz, P, Cz,
-             (float*)ws);
+  FRL_LAUNCH_AS(LOSS ? "dec_mse_bwd_loss_kernel" : "dec_mse_bwd_kernel", kern, dim3(grid), dim3(64 * NW), lds, st, (const TT*)z, (const frag8*)pk, b1, b2, (const TT*)tgt, mask, gscale, stats, (TT*)dz, P, Cz,
+             (float*)ws, la);
+  if constexpr (LOSS) {
+    FRL_LAUNCH(dec_mse_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)la.partial, (int)grid, la.out_w);
+    *nslab_out = (int)grid;
+    return frl_check_launch("decoder_mse_fwd_bwd");
+  }
   launch_slab_reduce_deferrable<float, DecEpi>((const float*)ws, (int)grid, (int64_t)slab_n, DecEpi{dw2, dw1, db2, db1, Cz, CZP, DF_F, DF_H}, st);
   return frl_check_launch("decoder_mse_bwd");
 }
 
 // two independent 4-wave subgroups per workgroup (64-row tiles each), a slab per subgroup
-template <int NFZ>
+template <int NFZ, bool LOSS = false>
 static int launch_dec_bwd_sg(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* tgt,
                              const uint8_t* mask, const float* gscale, const float* stats, void* dz, float* dw1, float* db1, float* dw2,
-                             float* db2, int64_t P, int Cz, char* ws, hipStream_t st) {
+                             float* db2, int64_t P, int Cz, char* ws, hipStream_t st, DecLoss<LOSS> la = DecLoss<LOSS>{}, int* nslab_out = nullptr) {
   constexpr int CZP = 32 * NFZ, CB = CZP / 16, R = 64;
   int64_t g = (P + 2 * R - 1) / (2 * R);
   if (g > 256) g = 256;
@@ -429,10 +515,15 @@ static int launch_dec_bwd_sg(const void* z, const float* w1, const float* b1, co
   const frag8* pk = dec_packed<NFZ>(w1, w2, Cz, 1, reinterpret_cast<frag8*>(ws + ((nslab * slab_n * sizeof(float) + 255) / 256) * 256), st);
   const size_t lds = (size_t)(8 * NFZ + 16 + 16 + CB * 4) * 64 * sizeof(frag8) + (192 + 32) * sizeof(float) +
                      (size_t)2 * R * ((DF_F + 8) + 2 * (DF_H + 8) + (CZP + 8)) * sizeof(TT);
-  auto kern = dec_mse_bwd_kernel<NFZ, 4, true>;
+  auto kern = dec_mse_bwd_kernel<NFZ, 4, true, LOSS>;
   FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  FRL_LAUNCH_AS("dec_mse_bwd_sg_kernel", kern, dim3(grid), dim3(512), lds, st, (const TT*)z, (const frag8*)pk, b1, b2, (const TT*)tgt, mask, gscale, stats, (TT*)dz, P,
-                Cz, (float*)ws);
+  FRL_LAUNCH_AS(LOSS ? "dec_mse_bwd_sg_loss_kernel" : "dec_mse_bwd_sg_kernel", kern, dim3(grid), dim3(512), lds, st, (const TT*)z, (const frag8*)pk, b1, b2, (const TT*)tgt, mask, gscale, stats, (TT*)dz, P,
+                Cz, (float*)ws, la);
+  if constexpr (LOSS) {
+    FRL_LAUNCH(dec_mse_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)la.partial, (int)grid, la.out_w);
+    *nslab_out = (int)nslab;
+    return frl_check_launch("decoder_mse_fwd_bwd");
+  }
   launch_slab_reduce_deferrable<float, DecEpi>((const float*)ws, (int)nslab, (int64_t)slab_n, DecEpi{dw2, dw1, db2, db1, Cz, CZP, DF_F, DF_H}, st);
   return frl_check_launch("decoder_mse_bwd");
 }
@@ -495,6 +586,52 @@ int frl_decoder_mse_bwd(const void* z, const float* w1, const float* b1, const f
     return launch_dec_bwd_sg<1>(z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream);
   if (Cz <= 32) return launch_dec_bwd<1, 8>(z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream);
   return launch_dec_bwd<2, 4>(z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream);
+}
+
+// ---- one pass (train step) ----
+// buffer of a one-pass call: the layout of the backward workspace (slabs | packed weights) followed by the workgroups' loss partials
+static size_t df_onepass_partial_off(int64_t P, int Cz) { return ((frl_decoder_mse_workspace_bytes(P, Cz) + 255) / 256) * 256; }
+size_t frl_decoder_mse_onepass_bytes(int64_t P, int Cz) { return df_onepass_partial_off(P, Cz) + (size_t)256 * 2 * sizeof(double); }
+
+// Loss AND gradients from one pass over (z, target): the backward kernels of frl_decoder_mse_bwd with the loss accumulated on the side.
+// gscale: device scalar, the gradient the caller promises the loss will receive (null: 1).  out = {loss, n_valid} as frl_decoder_mse_fwd
+// writes it; dz as frl_decoder_mse_bwd writes it.  The weight-gradient slabs stay unreduced in `buf` (which the caller keeps untouched until
+// frl_decoder_mse_reduce on it has run -- inside frl_defer_begin/flush: until the flush); *nslab receives their number.  ctl: 4 zeroed
+// 32-bit words that no concurrent call shares (the mask count's ticket and total; the call leaves them zero).
+int frl_decoder_mse_fwd_bwd(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* target,
+                            const uint8_t* mask, const float* gscale, float* out, void* dz, void* buf, size_t buf_bytes, void* ctl,
+                            int* nslab, int64_t P, int Cz, hipStream_t stream) {
+  if (P <= 0) return frl_fail(-2, "decoder_mse_fwd_bwd: empty input");
+  if (Cz < 1 || Cz > 64) return frl_fail(-2, "decoder_mse_fwd_bwd: latent width must be 1..64");
+  if (buf_bytes < frl_decoder_mse_onepass_bytes(P, Cz)) return frl_fail(-4, "decoder_mse_fwd_bwd: buffer too small");
+  if (out == nullptr || dz == nullptr || ctl == nullptr || nslab == nullptr) return frl_fail(-2, "decoder_mse_fwd_bwd: null output");
+  unsigned* c = (unsigned*)ctl;
+  DecLoss<true> la;
+  la.partial = reinterpret_cast<double*>((char*)buf + df_onepass_partial_off(P, Cz));
+  la.out = out;
+  la.out_w = out;
+  la.nv_host = (float)((double)P * (double)DF_F);
+  if (mask != nullptr) {
+    int64_t g = (P + 256 * 64 - 1) / (256 * 64);
+    if (g > 128) g = 128;
+    FRL_LAUNCH(dec_mask_count_kernel, dim3((unsigned)g), dim3(256), 0, stream, mask, P, c, out);
+    la.nv_host = -1.f;
+  }
+  if (g_dec_subgroups && P >= 128 && Cz <= 32)
+    return launch_dec_bwd_sg<1, true>(z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab);
+  if (Cz <= 32)
+    return launch_dec_bwd<1, 8, true>(z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab);
+  return launch_dec_bwd<2, 4, true>(z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab);
+}
+
+// The slab reduction of a one-pass call: buf / nslab from frl_decoder_mse_fwd_bwd -> dw1 [128][Cz], db1 [128], dw2 [64][128], db2 [64], in the
+// summation order of frl_decoder_mse_bwd.  Parked when a deferral is open (it then launches nothing), else a launch on `stream`.
+int frl_decoder_mse_reduce(const void* buf, int nslab, float* dw1, float* db1, float* dw2, float* db2, int Cz, hipStream_t stream) {
+  if (Cz < 1 || Cz > 64 || nslab < 1 || nslab > 512) return frl_fail(-2, "decoder_mse_reduce: bad latent width or slab count");
+  const int czp = Cz <= 32 ? 32 : 64;
+  const size_t slab_n = (size_t)DF_F * DF_H + DF_H * czp + DF_F + DF_H;
+  launch_slab_reduce_deferrable<float, DecEpi>((const float*)buf, nslab, (int64_t)slab_n, DecEpi{dw2, dw1, db2, db1, Cz, czp, DF_F, DF_H}, stream);
+  return frl_check_launch("decoder_mse_reduce");
 }
 
 }  // extern "C"

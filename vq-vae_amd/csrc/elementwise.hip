@@ -224,10 +224,14 @@ __global__ void scalar_combine_kernel(ScalarTerms t, int n, float* __restrict__ 
   if (ok_out != nullptr) ok_out[0] = (s * 0.f == 0.f) ? 1.f : 0.f;   // x * 0 == 0 holds exactly for finite x
   if (aux_out != nullptr) aux_out[0] = a;
 }
-__global__ void scalar_fanout_kernel(const float* __restrict__ g, ScalarTerms t, int n, float* __restrict__ out) {
+// t.p[i] (optional, backward only): a device scalar holding the gradient that term i was PROMISED at forward time (a one-pass decoder loss
+// computed its gradients with it: dec_fused.hip); a term that receives anything else raises `flag` (a sticky device word the host polls).
+__global__ void scalar_fanout_kernel(const float* __restrict__ g, ScalarTerms t, int n, float* __restrict__ out, int* __restrict__ flag) {
   if ((int)threadIdx.x < n) {
     const int i = threadIdx.x;
-    out[i] = g[0] * (t.m[i] != nullptr ? t.c[i] * *t.m[i] : t.c[i]);
+    const float v = g[0] * (t.m[i] != nullptr ? t.c[i] * *t.m[i] : t.c[i]);
+    out[i] = v;
+    if (flag != nullptr && t.p[i] != nullptr && !(*t.p[i] == v)) flag[0] = 1;
   }
 }
 
@@ -237,6 +241,8 @@ int frl_scalar_combine_dev(const float* const* terms_host, const float* coef_hos
 int frl_scalar_combine_aux(const float* const* terms_host, const float* coef_host, const float* const* mult_host, const float* aux_coef_host, int n,
                            float* out, float* ok_out, float* aux_out, hipStream_t stream);
 int frl_scalar_fanout_dev(const float* g, const float* coef_host, const float* const* mult_host, int n, float* out, hipStream_t stream);
+int frl_scalar_fanout_guard(const float* g, const float* coef_host, const float* const* mult_host, const float* const* promise_host, int n,
+                            float* out, int* flag, hipStream_t stream);
 
 size_t frl_mse_workspace_bytes(void) { return (size_t)EW_GRID_MAX * 2 * sizeof(double); }
 
@@ -373,15 +379,22 @@ int frl_scalar_fanout(const float* g, const float* coef_host, int n, float* out,
   return frl_scalar_fanout_dev(g, coef_host, nullptr, n, out, stream);
 }
 int frl_scalar_fanout_dev(const float* g, const float* coef_host, const float* const* mult_host, int n, float* out, hipStream_t stream) {
+  return frl_scalar_fanout_guard(g, coef_host, mult_host, nullptr, n, out, nullptr, stream);
+}
+// The same with the promise check: promise_host (n device pointers, entries or the array may be NULL) names, per term, the gradient value
+// the term was promised in the forward; flag[0] (device int) is set to 1 when a term's gradient differs from its promise, else untouched.
+int frl_scalar_fanout_guard(const float* g, const float* coef_host, const float* const* mult_host, const float* const* promise_host, int n,
+                            float* out, int* flag, hipStream_t stream) {
   if (n < 1 || n > 8) return frl_fail(-2, "scalar_fanout: 1..8 terms");
+  if (promise_host != nullptr && flag == nullptr) return frl_fail(-2, "scalar_fanout: promises need a flag word");
   ScalarTerms t;
   for (int i = 0; i < 8; ++i) {
-    t.p[i] = nullptr;
+    t.p[i] = (i < n && promise_host != nullptr) ? promise_host[i] : nullptr;
     t.m[i] = (i < n && mult_host != nullptr) ? mult_host[i] : nullptr;
     t.c[i] = i < n ? coef_host[i] : 0.f;
     t.a[i] = 0.f;
   }
-  FRL_LAUNCH(scalar_fanout_kernel, dim3(1), dim3(8), 0, stream, g, t, n, out);
+  FRL_LAUNCH(scalar_fanout_kernel, dim3(1), dim3(8), 0, stream, g, t, n, out, flag);
   return frl_check_launch("scalar_fanout");
 }
 

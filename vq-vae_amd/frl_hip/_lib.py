@@ -64,6 +64,7 @@ SIGNATURES = {
     "frl_scalar_combine_dev": (c_int, [P, P, P, I, P, P, P]),
     "frl_scalar_combine_aux": (c_int, [P, P, P, P, I, P, P, P, P]),
     "frl_scalar_fanout_dev": (c_int, [P, P, P, I, P, P]),
+    "frl_scalar_fanout_guard": (c_int, [P, P, P, P, I, P, P, P]),
     "frl_encoder2_supported": (c_int, [I, I, I, I, I, I, I]),
     "frl_encoder2_workspace_bytes": (S, [I]),
     "frl_encoder2_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, F, P, S, P]),
@@ -72,6 +73,9 @@ SIGNATURES = {
     "frl_decoder_mse_workspace_bytes": (S, [L, I]),
     "frl_decoder_mse_fwd": (c_int, [P, P, P, P, P, P, P, P, P, L, I, P, S, P]),
     "frl_decoder_mse_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, P, S, P]),
+    "frl_decoder_mse_onepass_bytes": (S, [L, I]),
+    "frl_decoder_mse_fwd_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, S, P, P, L, I, P]),
+    "frl_decoder_mse_reduce": (c_int, [P, I, P, P, P, P, I, P]),
     "frl_mse_workspace_bytes": (S, []),
     "frl_mse_fwd": (c_int, [P, P, P, L, I, P, I, P, S, P]),
     "frl_mse_bwd": (c_int, [P, P, P, P, P, L, I, P, I, P]),

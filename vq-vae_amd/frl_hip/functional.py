@@ -120,18 +120,19 @@ class ScalarCombineFn(Function):
     combination of the same terms); backward: one launch for all term gradients."""
 
     @staticmethod
-    def forward(ctx, coefs, mults, aux_coefs, *terms):
+    def forward(ctx, coefs, mults, aux_coefs, promises, *terms):
         res = ops.scalar_combine([t.detach() for t in terms], coefs, mults, aux_coefs)
         ctx.coefs = tuple(float(c) for c in coefs)
         ctx.mults = mults                                           # device scalars (no gradient: schedule values), read again in the backward
+        ctx.promises = promises                                     # per term: the gradient it was promised (one-pass decoder loss) | None
         ctx.mark_non_differentiable(*res[1:])
         return res if aux_coefs is not None else res + (None,)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g, g_ok, g_aux):
-        gg = ops.scalar_fanout(g.reshape(1).float().contiguous(), ctx.coefs, ctx.mults)
-        return (None, None, None) + tuple(gg[i] for i in range(len(ctx.coefs)))
+        gg = ops.scalar_fanout(g.reshape(1).float().contiguous(), ctx.coefs, ctx.mults, ctx.promises)
+        return (None, None, None, None) + tuple(gg[i] for i in range(len(ctx.coefs)))
 
 
 def scalar_combine(terms, coefs, mults=None, aux_coefs=None):
@@ -150,8 +151,15 @@ def scalar_combine(terms, coefs, mults=None, aux_coefs=None):
             return tot, None
         aux = sum(float(c) * t.detach() for t, c in zip(terms, aux_coefs))
         return tot, None, aux
+    # a term computed for a promised upstream gradient (decoder_mse(..., grad_scale=)) has it checked inside the backward's one launch
+    promises = []
+    for t in terms:
+        pr = getattr(t, "_frl_promise", None)
+        promises.append(None if pr is None else pr[0])
+        if pr is not None:
+            pr[1]["guarded"] = True
     loss, ok, aux = ScalarCombineFn.apply(tuple(coefs), None if mults is None else tuple(mults), None if aux_coefs is None else tuple(aux_coefs),
-                                          *[t.reshape(()) for t in terms])
+                                          tuple(promises) if any(p is not None for p in promises) else None, *[t.reshape(()) for t in terms])
     return (loss, ok) if aux_coefs is None else (loss, ok, aux)
 
 
@@ -472,12 +480,20 @@ class MseFn(Function):
 
 
 class DecoderMseFn(Function):
-    """Fused conv1x1 -> ReLU -> conv1x1 -> masked L2 loss: (z, W1, b1, W2, b2, target, mask) -> (loss, xhat | None)."""
+    """Fused conv1x1 -> ReLU -> conv1x1 -> masked L2 loss: (z, W1, b1, W2, b2, target, mask) -> (loss, xhat | None).
+    onepass = (grad_scale, state): the gradients are computed with the loss, in the forward, for the promised upstream gradient grad_scale
+    (ops.decoder_mse_fwd_bwd); the backward hands them out and launches at most the slab reduction."""
 
     @staticmethod
-    def forward(ctx, z, w1, b1, w2, b2, target, mask, want_xhat):
-        stats, xhat = ops.decoder_mse_fwd(z, w1, b1, w2, b2, target, mask, want_xhat)
+    def forward(ctx, z, w1, b1, w2, b2, target, mask, want_xhat, onepass=None):
         ctx.set_materialize_grads(False)
+        ctx.onepass = onepass
+        if onepass is not None:
+            stats, dz, slabs = ops.decoder_mse_fwd_bwd(z, w1, b1, w2, b2, target, mask, onepass[0])
+            ctx.held = (dz, slabs)
+            ctx.save_for_backward(w1, b1, w2, b2)
+            return stats.narrow(0, 0, 1).reshape(()), None
+        stats, xhat = ops.decoder_mse_fwd(z, w1, b1, w2, b2, target, mask, want_xhat)
         ctx.save_for_backward(z, w1, b1, w2, b2, target, mask, stats)
         if xhat is not None:
             ctx.mark_non_differentiable(xhat)
@@ -486,16 +502,45 @@ class DecoderMseFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, g_xhat):
+        if ctx.onepass is not None:
+            held, ctx.held = ctx.held, None                        # (no reference of ours survives: autograd adopts the tensors)
+            if held is None:
+                raise RuntimeError("decoder_mse: the gradients of a one-pass loss (grad_scale=) are handed out once; a second backward "
+                                   "through it needs the two-kernel path (grad_scale=None)")
+            if g is None:
+                return (None,) * 9
+            grad_scale, state = ctx.onepass
+            if not state["guarded"]:                                # the loss did not go through scalar_combine: check the promise here
+                ops.scalar_fanout(g.reshape(1).float().contiguous(), (1.0,), None, (grad_scale,))
+            dz, slabs = held
+            w1, b1, w2, b2 = ctx.saved_tensors
+            gw = (None,) * 4
+            if any(ctx.needs_input_grad[1:5]):
+                dw1, db1, dw2, db2 = ops.decoder_mse_reduce(slabs, w1, b1, w2, b2)
+                gw = _wanted(ctx, 1, (dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2))
+            del held, slabs
+            return (dz if ctx.needs_input_grad[0] else None,) + gw + (None, None, None, None)
         z, w1, b1, w2, b2, target, mask, stats = ctx.saved_tensors
         if g is None:
-            return (None,) * 8
+            return (None,) * 9
         dz, dw1, db1, dw2, db2 = ops.decoder_mse_bwd(z, w1, b1, w2, b2, target, mask, g.reshape(1).float().contiguous(), stats)
-        return _wanted(ctx, 0, (dz, dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2)) + (None, None, None)
+        return _wanted(ctx, 0, (dz, dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2)) + (None, None, None, None)
 
 
-def decoder_mse(z, w1, b1, w2, b2, target, mask=None, want_xhat=False):
+def decoder_mse(z, w1, b1, w2, b2, target, mask=None, want_xhat=False, grad_scale=None):
+    """-> (loss, xhat | None).  grad_scale (device float32 scalar): the gradient the caller PROMISES the returned loss will receive in the
+    backward (its coefficient in the total loss, the total being differentiated with upstream 1).  Loss and gradients then come from ONE
+    pass over (z, target) in the forward, when gradients are enabled, an input needs one and xhat is not asked for; otherwise, and without
+    grad_scale, the forward and backward kernels run as a pair.  A backward that delivers another gradient than promised raises the flag
+    behind ops.grad_scale_errors() / ops.check_grad_scale()."""
     if mask is not None:
         mask = mask.reshape(-1).to(torch.uint8).contiguous()
+    if (grad_scale is not None and not want_xhat and torch.is_grad_enabled()
+            and any(torch.is_tensor(t) and t.requires_grad for t in (z, w1, b1, w2, b2))):
+        state = {"guarded": False}
+        loss, xhat = DecoderMseFn.apply(z, w1, b1, w2, b2, target, mask, False, (grad_scale, state))
+        loss._frl_promise = (grad_scale, state)
+        return loss, xhat
     return DecoderMseFn.apply(z, w1, b1, w2, b2, target, mask, want_xhat)
 
 

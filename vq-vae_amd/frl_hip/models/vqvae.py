@@ -149,6 +149,11 @@ class VQVAE(RepresentationModel):
         self.defer_codebook_hooks = False                   # set by a trainer with an isfinite guard: see commit_codebook_hooks
         self._pending_manager = None
         self.fused_decoder = True
+        # train-mode forward_tiles: each decoder's loss AND gradients from one pass (Fh.decoder_mse(..., grad_scale=lambda_recon)), on the
+        # promise that out["loss"] is differentiated with upstream 1.  False: the forward / backward kernel pair (A/B runs, and callers
+        # that scale out["loss"] before .backward() -- a broken promise is reported by ops.check_grad_scale()).
+        self.onepass_decoder = True
+        self._grad_scale_dev = {}
         # The phase path is conditioned on stopgrad(z_type): forward AND backward of the two branches are independent, so the phase
         # branch runs on a side HIP stream next to VQ + type decoder (forward) and next to the whole type-path backward.
         self.concurrent_phase = True
@@ -167,19 +172,29 @@ class VQVAE(RepresentationModel):
         upd = getattr(manager, "update", None)
         self._manager_takes_rows = upd is not None and len(inspect.signature(upd).parameters) >= 2
 
-    def _decode_loss(self, dec: Conv2DHead, z: torch.Tensor, target: torch.Tensor, mask, want_recon: bool):
-        """Decoder + masked L2.  Hot configuration (bf16, hidden 128, 64 features): one fused kernel per direction, the
-        reconstruction is materialised only on request; otherwise the modular conv1x1 / MSE kernels."""
+    def _grad_scale(self, device) -> torch.Tensor:
+        """lambda_recon as a cached device scalar (a captured step must not allocate one per replay)."""
+        key = (str(device), float(self.lambda_recon))
+        t = self._grad_scale_dev.get(key)
+        if t is None:
+            t = self._grad_scale_dev[key] = torch.full((1,), float(self.lambda_recon), dtype=torch.float32, device=device)
+        return t
+
+    def _decode_loss(self, dec: Conv2DHead, z: torch.Tensor, target: torch.Tensor, mask, want_recon: bool, onepass: bool = False):
+        """Decoder + masked L2.  Hot configuration (bf16, hidden 128, 64 features): one fused kernel per direction -- or, with `onepass`
+        (train step: the loss enters the total with the weight lambda_recon), one kernel for both; the reconstruction is materialised only
+        on request; otherwise the modular conv1x1 / MSE kernels."""
         l0, l2 = dec.layers[0], dec.layers[-1]
         if (len(dec.layers) == 3 and self.fused_decoder
                 and ops.decoder_mse_supported(z.shape[-1], l0.out_channels, l2.out_channels, z)):
             w1 = l0.weight.reshape(l0.out_channels, l0.in_channels)
             w2 = l2.weight.reshape(l2.out_channels, l2.in_channels)
-            return Fh.decoder_mse(z, w1, l0.bias, w2, l2.bias, target, mask, want_recon)
+            gs = self._grad_scale(z.device) if (onepass and self.onepass_decoder and not want_recon) else None
+            return Fh.decoder_mse(z, w1, l0.bias, w2, l2.bias, target, mask, want_recon, grad_scale=gs)
         xhat = dec(z)
         return Fh.mse_loss(xhat, target, mask), xhat
 
-    def _phase_branch(self, tile, z_type_detached, mask, return_recon) -> Dict[str, torch.Tensor]:
+    def _phase_branch(self, tile, z_type_detached, mask, return_recon, onepass: bool = False) -> Dict[str, torch.Tensor]:
         """Dense phase path -> (optional phase codebook) -> phase decoder + masked L2; returns its outputs and `loss_terms`."""
         b, t, hh, ww, f = tile.shape
         out: Dict[str, torch.Tensor] = {}
@@ -195,7 +210,7 @@ class VQVAE(RepresentationModel):
             pmask = mask
         else:
             pmask = mask.unsqueeze(1).expand(b, t, hh, ww).contiguous()
-        l_phase, xhat_phase = self._decode_loss(self.decoder_phase, zp_in, tile, pmask, return_recon)
+        l_phase, xhat_phase = self._decode_loss(self.decoder_phase, zp_in, tile, pmask, return_recon, onepass)
         terms.append((l_phase, self.lambda_recon))
         out.update(z_phase=z_phase, l_phase=l_phase, loss_terms=terms)
         if xhat_phase is not None:
@@ -217,6 +232,9 @@ class VQVAE(RepresentationModel):
             x_type = ops.mean_time(tile)                                   # [B,H,W,F]
         z_type, gate = self.forward_nhwc(x_type, return_gate=True)          # [B,H,W,d]
         side = ph = None
+        # the decoder losses join the total below with the weight lambda_recon and out["loss"] is differentiated as it is (the legacy
+        # contract's caller builds its own total: no promise there)
+        onepass = self.training and not differentiable_vq_loss
         if self.phase and self.concurrent_phase and tile.is_cuda:
             main, side = torch.cuda.current_stream(), self.phase_stream(tile.device)
             side.wait_stream(main)
@@ -226,14 +244,14 @@ class VQVAE(RepresentationModel):
             if mask is not None:
                 mask.record_stream(side)
             with torch.cuda.stream(side):
-                ph = self._phase_branch(tile, zt, mask, return_recon)
+                ph = self._phase_branch(tile, zt, mask, return_recon, onepass)
         d = z_type.shape[-1]
         # gradient quantizer on the GPU: its two loss parts join the total below directly (one launch yields the total, the flag and vq_loss)
         split_vq = self.quant.quantizer != "ema" and z_type.is_cuda and not differentiable_vq_loss
         zq, vq_loss, perp, idx = self.quant(z_type.reshape(-1, d), raw_terms=split_vq)
         vq_parts = vq_loss if split_vq else None
         tmask = mask.amin(dim=1) if (mask is not None and mask.dim() == 4) else mask
-        l_type, xhat_type = self._decode_loss(self.decoder_type, zq.reshape(b, hh, ww, d), x_type, tmask, return_recon)
+        l_type, xhat_type = self._decode_loss(self.decoder_type, zq.reshape(b, hh, ww, d), x_type, tmask, return_recon, onepass)
         out = dict(z_type=z_type, gate=gate, idx=idx, vq_loss=None if split_vq else vq_loss, perplexity=perp, l_type=l_type,
                    vq_stats=self.quant.last_stats)
         if xhat_type is not None:
@@ -254,7 +272,7 @@ class VQVAE(RepresentationModel):
                     if torch.is_tensor(v):
                         v.record_stream(main)
             else:
-                ph = self._phase_branch(tile, z_type.detach(), mask, return_recon)
+                ph = self._phase_branch(tile, z_type.detach(), mask, return_recon, onepass)
             terms += ph.pop("loss_terms")
             out.update(ph)
         # weighted sum of the loss terms and its isfinite flag in ONE launch (the trainer's device-side guard reads out["loss_ok"])

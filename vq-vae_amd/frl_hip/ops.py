@@ -458,13 +458,61 @@ def scalar_combine(terms, coefs, mults=None, aux_coefs=None):
     return out, ok, aux
 
 
-def scalar_fanout(g, coefs, mults=None):
-    """g device float scalar -> out [n] f32 with out[i] = g * coef_i (* mult_i)."""
+def scalar_fanout(g, coefs, mults=None, promises=None):
+    """g device float scalar -> out [n] f32 with out[i] = g * coef_i (* mult_i).  promises: per term None or the device float scalar the
+    term's gradient was promised to equal at forward time (decoder_mse_fwd_bwd); a mismatch raises the flag behind `grad_scale_errors()`."""
     n = len(coefs)
     cf = (ctypes.c_float * n)(*[float(c) for c in coefs])
     out = torch.empty(n, dtype=torch.float32, device=g.device)
-    check(_lib.load().frl_scalar_fanout_dev(_p(g), cf, _mult_ptrs(mults, n), n, _p(out), _stream()), "frl_scalar_fanout")
+    if promises is None or all(p is None for p in promises):
+        check(_lib.load().frl_scalar_fanout_dev(_p(g), cf, _mult_ptrs(mults, n), n, _p(out), _stream()), "frl_scalar_fanout")
+        return out
+    for p in promises:
+        if p is not None and (p.dtype != torch.float32 or p.numel() != 1 or p.device != g.device):
+            raise ValueError("scalar_fanout: promises are float32 scalars on the gradient's device")
+    pp = (ctypes.c_void_p * n)(*[0 if p is None else p.data_ptr() for p in promises])
+    check(_lib.load().frl_scalar_fanout_guard(_p(g), cf, _mult_ptrs(mults, n), pp, n, _p(out), _p(_grad_scale_flag(g.device)), _stream()),
+          "frl_scalar_fanout_guard")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# The promise behind the one-pass decoder loss (decoder_mse_fwd_bwd): its gradients are computed in the forward with the upstream
+# gradient the caller announced.  The backward compares what arrives with the promise on the device (inside the launch that computes the
+# term gradients: no extra launch, no host sync) and raises a sticky per-device flag; `grad_scale_errors()` reads it where the host
+# synchronises anyway (the trainer's logging path), as `index_errors()` does for the sparse ops.
+# ----------------------------------------------------------------------------------------------
+_GRAD_SCALE_FLAG = {}
+
+
+def _grad_scale_flag(device) -> torch.Tensor:
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    flag = _GRAD_SCALE_FLAG.get(device)
+    if flag is None:
+        flag = _GRAD_SCALE_FLAG[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return flag
+
+
+def grad_scale_errors(device=None, reset: bool = True) -> bool:
+    """True when a loss computed with a promised upstream gradient (decoder_mse(..., grad_scale=)) received another one in a backward since
+    the last call on `device` (all devices when None): the gradients of that backward are wrongly scaled.  Synchronises."""
+    hit = False
+    for dev, flag in _GRAD_SCALE_FLAG.items():
+        if device is None or torch.device(device) == dev:
+            hit |= bool(flag.item())
+            if reset:
+                flag.zero_()
+    return hit
+
+
+def check_grad_scale(device=None) -> None:
+    """Raises when `grad_scale_errors()` reports a broken promise (and clears the flag)."""
+    if grad_scale_errors(device):
+        raise RuntimeError("decoder_mse: a loss whose gradients were computed in the forward for a promised upstream gradient (grad_scale) "
+                           "received a different one in the backward -- the decoder gradients of that step are wrongly scaled.  Scale the "
+                           "loss through the promised coefficient, or switch the one-pass path off (VQVAE.onepass_decoder = False)")
 
 
 def encoder2_supported(c0: int, c1: int, c2: int, g1: int, g2: int, hw: int, dtype) -> bool:
@@ -1152,6 +1200,50 @@ def decoder_mse_bwd(z, w1, b1, w2, b2, target, mask, gscale, stats):
     check(lib.frl_decoder_mse_bwd(_p(z), _p(w1), _p(b1), _p(w2), _p(b2), _p(target), _p(mask), _p(gscale), _p(stats), _p(dz), _p(dw1),
                                   _p(db1), _p(dw2), _p(db2), p, cz, _p(ws), ws.numel(), _stream()), "frl_decoder_mse_bwd")
     return dz, dw1, db1, dw2, db2
+
+
+_DEC_CTL = {}
+
+
+def _dec_ctl(device) -> torch.Tensor:
+    """Zeroed control words of the one-pass decoder kernels, one set per (device, stream): calls on one stream are ordered and every call
+    leaves them zero."""
+    key = (str(device), torch.cuda.current_stream().cuda_stream)
+    c = _DEC_CTL.get(key)
+    if c is None:
+        c = _DEC_CTL[key] = torch.zeros(4, dtype=torch.int32, device=device)
+    return c
+
+
+@_timed("decoder_mse_fwd_bwd")
+def decoder_mse_fwd_bwd(z, w1, b1, w2, b2, target, mask, grad_scale):
+    """Loss and gradients in one pass (train step): -> (stats f32 [2] = {mse, n_valid}, dz, slabs).  grad_scale: device float32 scalar, the
+    gradient the loss will receive (None: 1).  `slabs` = (buffer, count) goes to `decoder_mse_reduce` for the weight gradients."""
+    cz = z.shape[-1]
+    p = z.numel() // cz
+    lib = _lib.load()
+    if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 or grad_scale.device != z.device):
+        raise ValueError("decoder_mse_fwd_bwd: grad_scale is a float32 scalar on the input's device")
+    buf = torch.empty(lib.frl_decoder_mse_onepass_bytes(p, cz), dtype=torch.uint8, device=z.device)     # (its own: it outlives the call)
+    out = torch.empty(2, dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z)
+    nslab = ctypes.c_int(0)
+    check(lib.frl_decoder_mse_fwd_bwd(_p(z), _p(w1), _p(b1), _p(w2), _p(b2), _p(target), _p(mask), _p(grad_scale), _p(out), _p(dz), _p(buf),
+                                      buf.numel(), _p(_dec_ctl(z.device)), ctypes.cast(ctypes.byref(nslab), ctypes.c_void_p), p, cz, _stream()),
+          "frl_decoder_mse_fwd_bwd")
+    return out, dz, (buf, int(nslab.value))
+
+
+@_timed("decoder_mse_reduce")
+def decoder_mse_reduce(slabs, w1, b1, w2, b2):
+    """The weight gradients of a `decoder_mse_fwd_bwd` call from its slabs: parked inside `deferred_reductions` (no launch), else one launch."""
+    buf, nslab = slabs
+    cz = w1.shape[-1]
+    if _DEFER["on"]:
+        _DEFER["keep"].append(buf)                              # read by the flush
+    dw1, db1, dw2, db2 = (grad_empty(t.shape, buf.device) for t in (w1, b1, w2, b2))
+    check(_lib.load().frl_decoder_mse_reduce(_p(buf), nslab, _p(dw1), _p(db1), _p(dw2), _p(db2), cz, _stream()), "frl_decoder_mse_reduce")
+    return dw1, db1, dw2, db2
 
 
 # ----------------------------------------------------------------------------------------------

@@ -78,7 +78,15 @@ class VQVAETrainer:
     @property
     def n_skipped(self) -> int:
         """Batches skipped by the isfinite guard (reads the device counter when the HIP optimizer is in use)."""
+        self.check_promises()
         return self.opt.applied_and_skipped[1] if self.hip_opt else self.skipped
+
+    def check_promises(self) -> None:
+        """Raises when a step differentiated a one-pass decoder loss with another upstream gradient than it was computed for
+        (ops.check_grad_scale).  Reads a device flag: called where the host synchronises anyway (skip counter, evaluation, logging)."""
+        if self.params and self.params[0].is_cuda:
+            from .. import ops
+            ops.check_grad_scale(self.params[0].device)
 
     def set_epoch(self, epoch: int):
         """Per-epoch curricula: beta schedule of configs/vae_v0.yaml:21-27."""
@@ -394,6 +402,7 @@ class VQVAETrainer:
             return res
         parts = [acc] + [x.double() for x in (counts, counts_p) if x is not None]
         host = torch.cat(parts).cpu().split([t.numel() for t in parts])                 # the one host synchronisation
+        self.check_promises()
         a = host[0]
         n_ok = int(a[4].item())
         for j, name in enumerate(("loss", "l_type", "l_phase", "vq_loss")):
