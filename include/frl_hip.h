@@ -456,6 +456,19 @@ int frl_infonce_fwd(const float* emb, int D, const int64_t* pairs, const float* 
 int frl_infonce_pair_grads(const float* emb, int D, const int64_t* pairs, const float* sims, const float* coef, const float* gscale, int64_t T,
                            int64_t nseg, float temperature, int similarity, float* ga, float* gb, frl_stream_t stream);
 
+/* ---- VICReg variance-covariance loss (csrc/vicreg.hip) ----------------------------------------------------------------------
+ * variance_covariance_loss of frl/losses/variance_covariance.py:14-88 over rows x [N][D] (dtype 0 = float32, 1 = bfloat16; N >= 2,
+ * 1 <= D <= 128; f32 statistics): cov = Xc^T Xc / (N-1) with the moments taken about a pivot p = the mean of the first min(N, 64) rows
+ * (no cancellation against the mean), losses [3] = (total, variance_loss, covariance_loss).  cov [D][D] and centre [2][D] = p | mean - p
+ * are written when both are non-NULL (a gradient is wanted) and are what frl_vicreg_bwd reads:  dx = ((x - p) - (mean - p)) A,  A built on the device from cov and
+ * g3 [3] = the upstream gradients of (total, variance_loss, covariance_loss); dx has the dtype of x.  No float atomics: both calls are
+ * bit-reproducible.  Workspace: frl_vicreg_workspace_bytes(N, D). */
+size_t frl_vicreg_workspace_bytes(int64_t N, int D);
+int frl_vicreg_fwd(const void* x, int64_t N, int D, int dtype, float variance_weight, float covariance_weight, float variance_target,
+                   float eps, float* losses, float* cov, float* centre, void* ws, size_t ws_bytes, frl_stream_t stream);
+int frl_vicreg_bwd(const void* x, const float* cov, const float* centre, const float* g3, int64_t N, int D, int dtype, float variance_weight,
+                   float covariance_weight, float variance_target, float eps, void* dx, frl_stream_t stream);
+
 /* ---- code-map decoding (csrc/codes.hip) --------------------------------------------------------------------------------------
  * frl_decode_codes: out[p][:] = table[idx[p]][:] for a decoded-code table [K][F] (dtype 0 = float32, 1 = bfloat16; the VQ-VAE decoder
  * applied to the K codebook rows), idx [P] int32.  Indices in [-K, 0) wrap to idx + K; any other out-of-range index is clamped into

@@ -150,6 +150,9 @@ SIGNATURES = {
     "frl_tcn_chain_fwd": (c_int, [P] * 13 + [L, I, I, F, P, S, P]),
     "frl_tcn_block_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, F, I, P, S, P]),
     "frl_decode_codes": (c_int, [P, P, P, L, I, I, I, P, P]),
+    "frl_vicreg_workspace_bytes": (S, [L, I]),
+    "frl_vicreg_fwd": (c_int, [P, L, I, I, F, F, F, F, P, P, P, P, S, P]),
+    "frl_vicreg_bwd": (c_int, [P, P, P, P, L, I, I, F, F, F, F, P, P]),
 }
 
 

@@ -44,6 +44,11 @@ class VAEConfig:
     ema_decay: float = 0.99
     ema_eps: float = 1e-5
     lambda_vq: float = 1.0
+    # VICReg variance-covariance regulariser on the pre-quantisation latents (VQVAE lambda_vcr; 0 = off, the default)
+    lambda_vcr: float = 0.0
+    vcr_variance_weight: float = 1.0
+    vcr_covariance_weight: float = 1.0
+    vcr_variance_target: float = 1.0
     hidden: int = 128                     # decoder width (train_vqvae.py:413)
     min_lr: float = -1.0                  # < 0: optimizer.scheduler.eta_min (vae_v0.yaml) / 3e-5 of the legacy CLI when that is absent too
     lambda_cont: float = 1.0              # weight of the continuous reconstruction (= lambda_recon of the tile VQ-VAE)
@@ -81,6 +86,14 @@ def load_model_config(path: str) -> dict:
         return yaml.safe_load(f)
 
 
+def _vcr_kwargs(cfg: VAEConfig) -> Dict[str, Any]:
+    """Constructor arguments of the VICReg term; none when it is off, so that the model is built exactly as without the keys."""
+    if float(cfg.lambda_vcr) == 0.0:
+        return {}
+    return dict(lambda_vcr=float(cfg.lambda_vcr), vcr_variance_weight=float(cfg.vcr_variance_weight),
+                vcr_covariance_weight=float(cfg.vcr_covariance_weight), vcr_variance_target=float(cfg.vcr_variance_target))
+
+
 def build_trainer_from_config(cfg: VAEConfig, steps_per_epoch: int, in_features: int = 64, device=None, compute_dtype=None,
                               model_kwargs: Dict[str, Any] = None):
     """The consumer `configs/vae_v0.yaml` lacks in the reference: VAEConfig -> (VQVAE, VQVAETrainer, CheckpointManager, run_dir).
@@ -109,7 +122,7 @@ def build_trainer_from_config(cfg: VAEConfig, steps_per_epoch: int, in_features:
     sched = cfg.optimizer.scheduler or {}
     if sched.get("name", "cosine") != "cosine":
         raise ValueError(f"optimizer.scheduler.name must be cosine, got {sched.get('name')!r}")
-    mk = dict(model_kwargs or {})
+    mk = {**_vcr_kwargs(cfg), **(model_kwargs or {})}          # an explicit model_kwargs entry wins over the config key
     if compute_dtype is not None:
         mk["compute_dtype"] = compute_dtype
     model = VQVAE(in_features=in_features, codebook_size=cfg.codebook_size, emb_dim=cfg.emb_dim, beta=cfg.beta, hidden=cfg.hidden,

@@ -1,2 +1,3 @@
 from .pairs import pairs_mutual_knn_chunked  # noqa: F401
 from .contrastive import contrastive_loss  # noqa: F401
+from .variance_covariance import variance_covariance_loss, variance_loss, covariance_loss  # noqa: F401

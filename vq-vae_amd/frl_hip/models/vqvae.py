@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import functional as Fh
 from .. import ops
+from ..losses.variance_covariance import variance_covariance_loss
 from .blocks import Conv2DHead
 from .representation import RepresentationModel
 
@@ -104,13 +105,22 @@ class VectorQuantizer(nn.Module):
 
 
 class VQVAE(RepresentationModel):
-    """Encoder -> VQ(z_type) -> type decoder ; phase path conditioned on stopgrad(z_type_cont) -> phase decoder."""
+    """Encoder -> VQ(z_type) -> type decoder ; phase path conditioned on stopgrad(z_type_cont) -> phase decoder.
+
+    lambda_vcr > 0 (with vcr_variance_weight, vcr_covariance_weight, vcr_variance_target) adds the VICReg variance-covariance
+    regulariser (losses.variance_covariance_loss) to the train-mode loss of forward_tiles: lambda_vcr * total over the z_type rows
+    [B*H*W, d] and, with a phase path, lambda_vcr * total over the z_phase rows [B*T*H*W, zp]; reported as out["vcr_loss"] /
+    out["vcr_loss_phase"].  The statistics are taken over ALL rows of the batch: pixels that `mask` marks invalid are included (the
+    mask weights the reconstruction losses only).  Data parallel: every rank takes the statistics of its own rows -- the reference
+    has no DDP, and the gradient buckets average the ranks' gradients as for every other term; statistics are not all-gathered.
+    lambda_vcr = 0 (default): no new code runs and no new key appears."""
 
     def __init__(self, in_features: Optional[int] = None, codebook_size: int = 256, emb_dim: int = 64, beta: float = 0.25,
                  hidden: int = 128, quantizer: str = "st", ema_decay: float = 0.99, ema_eps: float = 1e-5,
                  phase: bool = True, phase_codebook_size: int = 0, lambda_recon: float = 1.0, lambda_vq: float = 1.0,
                  cont_dim: Optional[int] = None, cat_vocab_sizes=None, naip_bands: Optional[int] = None, cat_emb_dim: int = 8,
-                 **repr_kwargs):
+                 lambda_vcr: float = 0.0, vcr_variance_weight: float = 1.0, vcr_covariance_weight: float = 1.0,
+                 vcr_variance_target: float = 1.0, **repr_kwargs):
         # Legacy constructor call (scripts/train_vqvae.py:183-195): VQVAE(cont_dim=, cat_vocab_sizes=, naip_bands=, emb_dim=,
         # codebook_size=, beta=, hidden=, quantizer=, cat_emb_dim=, ema_decay=, ema_eps=).  `cont_dim` is the number of continuous
         # features = the tile's feature axis (alias of in_features).  The tile VQ-VAE has no categorical embeddings and no NAIP
@@ -135,6 +145,15 @@ class VQVAE(RepresentationModel):
         super().__init__(type_in_channels=in_features, phase_in_channels=in_features, **repr_kwargs)
         self.in_features, self.phase, self.lambda_recon, self.lambda_vq = in_features, phase, lambda_recon, lambda_vq
         self.cont_dim, self.legacy_inputs = in_features, self_legacy
+        # VICReg variance-covariance regulariser on the pre-quantisation latents (losses.variance_covariance_loss): with lambda_vcr > 0 a
+        # train-mode forward_tiles adds lambda_vcr * total(z_type rows) -- and, with a phase path, lambda_vcr * total(z_phase rows) -- to
+        # the loss (class docstring: masked pixels, data parallel).  Third remedy against index collapse next to the data-dependent codebook
+        # init and the dead-code revival.  0 (default): nothing runs.
+        if lambda_vcr < 0:
+            raise ValueError("lambda_vcr must be >= 0")
+        self.lambda_vcr = float(lambda_vcr)
+        self.vcr_variance_weight, self.vcr_covariance_weight = float(vcr_variance_weight), float(vcr_covariance_weight)
+        self.vcr_variance_target = float(vcr_variance_target)
         self.quant = VectorQuantizer(codebook_size, emb_dim, beta, quantizer, ema_decay, ema_eps)
         self.decoder_type = Conv2DHead(emb_dim, [hidden], in_features)
         if phase:
@@ -180,6 +199,12 @@ class VQVAE(RepresentationModel):
             t = self._grad_scale_dev[key] = torch.full((1,), float(self.lambda_recon), dtype=torch.float32, device=device)
         return t
 
+    def _vcr_term(self, z: torch.Tensor):
+        """(total VICReg loss of the rows of z [..., d], lambda_vcr): a loss term for forward_tiles' weighted sum."""
+        total, _, _ = variance_covariance_loss(z.reshape(-1, z.shape[-1]), self.vcr_variance_weight, self.vcr_covariance_weight,
+                                               self.vcr_variance_target)
+        return (total, self.lambda_vcr)
+
     def _decode_loss(self, dec: Conv2DHead, z: torch.Tensor, target: torch.Tensor, mask, want_recon: bool, onepass: bool = False):
         """Decoder + masked L2.  Hot configuration (bf16, hidden 128, 64 features): one fused kernel per direction -- or, with `onepass`
         (train step: the loss enters the total with the weight lambda_recon), one kernel for both; the reconstruction is materialised only
@@ -212,6 +237,9 @@ class VQVAE(RepresentationModel):
             pmask = mask.unsqueeze(1).expand(b, t, hh, ww).contiguous()
         l_phase, xhat_phase = self._decode_loss(self.decoder_phase, zp_in, tile, pmask, return_recon, onepass)
         terms.append((l_phase, self.lambda_recon))
+        if self.lambda_vcr > 0 and self.training:
+            terms.append(self._vcr_term(z_phase))
+            out["vcr_loss_phase"] = terms[-1][0].detach()
         out.update(z_phase=z_phase, l_phase=l_phase, loss_terms=terms)
         if xhat_phase is not None:
             out["xhat_phase"] = xhat_phase
@@ -265,6 +293,9 @@ class VQVAE(RepresentationModel):
         else:
             terms = [(l_type, self.lambda_recon), self._vq_term(vq_loss)]
             aux = None
+        if self.lambda_vcr > 0 and self.training:
+            terms.append(self._vcr_term(z_type))
+            out["vcr_loss"] = terms[-1][0].detach()
         if self.phase:
             if side is not None:
                 main.wait_stream(side)

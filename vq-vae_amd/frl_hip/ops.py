@@ -1345,3 +1345,45 @@ def infonce_pair_grads(emb, pairs, sims, coef, gscale, nseg: int, temperature: f
     check(_lib.load().frl_infonce_pair_grads(_p(emb), d, _p(pairs), _p(sims), _p(coef), _p(gscale), t, nseg, float(temperature), int(sim),
                                              _p(ga), _p(gb), _stream()), "frl_infonce_pair_grads")
     return ga, gb
+
+
+# ----------------------------------------------------------------------------------------------
+# VICReg variance-covariance loss (csrc/vicreg.hip)
+# ----------------------------------------------------------------------------------------------
+def _chk_vicreg(x: torch.Tensor, name: str):
+    if not x.is_cuda:
+        raise _lib.FrlHipError(f"{name}: tensor must live on the GPU (no CPU fallback)")
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] < 2 or not (1 <= x.shape[1] <= 128):
+        raise ValueError(f"{name}: expected contiguous rows [N >= 2, 1 <= D <= 128], got {tuple(x.shape)} stride {x.stride()}")
+
+
+@_timed("vicreg_fwd")
+def vicreg_fwd(x: torch.Tensor, variance_weight: float = 1.0, covariance_weight: float = 1.0, variance_target: float = 1.0,
+               eps: float = 1e-4, want_grad: bool = True):
+    """x [N, D] (float32 | bfloat16) -> (losses f32 [3] = total, variance_loss, covariance_loss; cov f32 [D, D]; centre f32 [2, D] = the
+    pivot p (mean of the first 64 rows) | mean - p); cov and centre (what vicreg_bwd reads) are None unless want_grad."""
+    _chk_vicreg(x, "vicreg_fwd")
+    n, d = x.shape
+    losses = torch.empty(3, dtype=torch.float32, device=x.device)
+    cov = torch.empty(d, d, dtype=torch.float32, device=x.device) if want_grad else None
+    centre = torch.empty(2, d, dtype=torch.float32, device=x.device) if want_grad else None
+    lib = _lib.load()
+    ws = workspace(lib.frl_vicreg_workspace_bytes(n, d), x.device)
+    check(lib.frl_vicreg_fwd(_p(x), n, d, _dt(x), float(variance_weight), float(covariance_weight), float(variance_target), float(eps),
+                             _p(losses), _p(cov), _p(centre), _p(ws), ws.numel(), _stream()), "frl_vicreg_fwd")
+    return losses, cov, centre
+
+
+@_timed("vicreg_bwd")
+def vicreg_bwd(x: torch.Tensor, cov: torch.Tensor, centre: torch.Tensor, g3: torch.Tensor, variance_weight: float = 1.0,
+               covariance_weight: float = 1.0, variance_target: float = 1.0, eps: float = 1e-4) -> torch.Tensor:
+    """dx [N, D] in the dtype of x for the upstream gradients g3 f32 [3] of (total, variance_loss, covariance_loss), read on the device."""
+    _chk_vicreg(x, "vicreg_bwd")
+    n, d = x.shape
+    for t, shape, name in ((cov, (d, d), "cov"), (centre, (2, d), "centre"), (g3, (3,), "g3")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"vicreg_bwd: {name} must be a contiguous float32 {shape} tensor on the device of x")
+    dx = torch.empty_like(x)
+    check(_lib.load().frl_vicreg_bwd(_p(x), _p(cov), _p(centre), _p(g3), n, d, _dt(x), float(variance_weight), float(covariance_weight),
+                                     float(variance_target), float(eps), _p(dx), _stream()), "frl_vicreg_bwd")
+    return dx
