@@ -299,14 +299,11 @@ int frl_tcn_hot_bwd_head(const void* x, const void* dh, const float* head_w, int
                          const float* gn_w, const float* gn_b, const float* gate_w, const float* gate_b, void* dx, float* d_conv_w,
                          float* d_conv_b, float* d_gn_w, float* d_gn_b, float* d_gate_w, float* d_gate_b, int64_t npix, int HW,
                          int dilation, float eps, void* ws, size_t ws_bytes, frl_stream_t stream);
-/* Two kernels stand behind frl_tcn_hot_bwd: tcn_hot_bwd3 (no mask, HW a multiple of 64: x of a 64-pixel tile is staged once in LDS by
- * LDS-DMA, next tile prefetched) and the 8-wave kernel that also takes a mask and ragged pixel counts.  Test hook: on != 0 routes
- * every call through the latter so that the two can be compared on the same inputs. */
+/* Two kernels stand behind frl_tcn_hot_bwd: tcn_hot_bwd4_kernel (no mask, HW a multiple of 64: two independent 4-wave subgroups per
+ * workgroup, each staging x of its 32-pixel tiles once in LDS by LDS-DMA with the next tile prefetched) and tcn_hot_bwd2_kernel, the
+ * 8-wave kernel that also takes a mask and ragged pixel counts.  They agree up to the bf16 rounding of dx and of dres inside.  Test hook: on != 0
+ * routes every call through the latter so that the two can be compared on the same inputs. */
 int frl_tcn_hot_force_generic_tiles(int on);   /* returns the previous setting */
-/* Which kernel serves the unmasked, HW % 64 == 0 backward: 4 (default) = tcn_hot_bwd4_kernel (two independent 4-wave subgroups per
- * workgroup over 32-pixel tiles), 3 = tcn_hot_bwd3_kernel (8 waves in lockstep over 64-pixel tiles).  Same results up to the rounding
- * of dres (bf16); returns the previous setting.  For A/B measurements and the parity tests of both kernels. */
-int frl_tcn_hot_bwd_variant(int v);
 /* Tuning hook of tcn_hot_bwd4: subgroup 0's share (in 32nds, 1..31) of a workgroup's tiles for variant 0 (with dx), 1 (without dx), 2 (head);
  * returns the previous value (share outside 1..31: query only).  Any value gives the same gradients up to float32 summation order. */
 int frl_tcn_hot_bwd4_share(int variant, int share);

@@ -436,20 +436,14 @@ def test_tcn_hot_kernels_match_oracle_and_generic(B, HW, dil):
         assert rel_err(hot[kk].reshape(ref.shape), gen[kk].reshape(ref.shape).cpu()) <= 2e-2, kk
 
 
-@pytest.mark.parametrize("variant", [4, 3])
 @pytest.mark.parametrize("B,HW,dil", [(21, 1024, 1), (18, 1024, 2), (5, 4096, 4), (600, 64, 1), (3, 64, 2)])
-def test_tcn_hot_bwd_staged_tiles_match_the_8_wave_kernel(B, HW, dil, variant):
-    """frl_tcn_hot_bwd has three kernels (include/frl_hip.h): the LDS-staged ones (no mask, HW % 64 == 0; variant 4 = two independent
-    4-wave subgroups per workgroup over 32-pixel tiles, variant 3 = 8 waves in lockstep over 64-pixel tiles) must agree with the round-1
-    8-wave kernel on the same inputs to bf16 rounding of dx and to float32 summation order of the parameter gradients -- with MORE tiles
-    than workgroups (256), so that every workgroup / subgroup walks several tiles (next-tile LDS-DMA, X / N buffer swap), an uneven
-    number of tiles per subgroup, and a launch of three workgroups -- and twice in a row bit for bit (fixed-order reductions)."""
-    from frl_hip import ops, _lib
-    was = _lib.load().frl_tcn_hot_bwd_variant(variant)
-    try:
-        _staged_tiles_case(B, HW, dil)
-    finally:
-        _lib.load().frl_tcn_hot_bwd_variant(was)
+def test_tcn_hot_bwd_staged_tiles_match_the_8_wave_kernel(B, HW, dil):
+    """frl_tcn_hot_bwd has two kernels (include/frl_hip.h): the LDS-staged one (no mask, HW % 64 == 0; two independent 4-wave subgroups
+    per workgroup over 32-pixel tiles) must agree with the round-1 8-wave kernel on the same inputs to bf16 rounding of dx and to float32
+    summation order of the parameter gradients -- with MORE tiles than workgroups (256), so that every workgroup / subgroup walks several
+    tiles (next-tile LDS-DMA, X / N buffer swap), an uneven number of tiles per subgroup, and a launch of three workgroups -- and twice
+    in a row bit for bit (fixed-order reductions)."""
+    _staged_tiles_case(B, HW, dil)
 
 
 def _staged_tiles_case(B, HW, dil):
@@ -473,8 +467,8 @@ def _staged_tiles_case(B, HW, dil):
         lib.frl_tcn_hot_force_generic_tiles(0)
     for k in new:
         assert torch.equal(new[k], again[k]), k
-    # both round dx to bf16; variant 3 and the round-1 kernel also round the same dres = dy - dy g inside, variant 4 keeps dy g (rounded) and
-    # subtracts late, so a quarter of its dx elements land on the neighbouring bf16 value: one ulp = 2^-7 of the element at worst
+    # both round dx to bf16; the round-1 kernel also rounds dres = dy - dy g inside, the staged kernel keeps dy g (rounded) and subtracts
+    # late, so a quarter of its dx elements land on the neighbouring bf16 value: one ulp = 2^-7 of the element at worst
     d = (new["dx"].float() - old["dx"].float()).abs().cpu()
     assert d.max().item() <= 8e-3 * old["dx"].float().abs().max().item()
     assert d.mean().item() <= 2e-3 * old["dx"].float().abs().mean().item()

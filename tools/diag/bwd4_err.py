@@ -1,4 +1,4 @@
-"""tcn_hot_bwd4 against tcn_hot_bwd3 and the round-1 8-wave kernel on a multi-tile case: max / mean differences and launch time."""
+"""tcn_hot_bwd4 against the round-1 8-wave kernel on a multi-tile case: max / mean differences and launch time."""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "vq-vae_amd"))
 import torch
@@ -12,25 +12,20 @@ w = dict(conv_w=torch.randn(64, 64, 3, generator=g) / 192 ** 0.5, conv_b=torch.r
 args = tuple(w[k].cuda() for k in ("conv_w", "conv_b", "gn_w", "gn_b", "gate_w", "gate_b")) + (None, None)
 x = torch.randn(B, 5, HW, 64, generator=g).bfloat16().cuda()
 dy = torch.randn(B, 5, HW, 64, generator=g).bfloat16().cuda()
-out = {}
-for v in (4, 3):
-    lib.frl_tcn_hot_bwd_variant(v)
-    out[v] = ops.tcn_block_bwd(x, dy, *args, dil, 8)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10):
-        ops.tcn_block_bwd(x, dy, *args, dil, 8)
-    e1.record()
-    torch.cuda.synchronize()
-    print(f"variant {v}: {e0.elapsed_time(e1) * 100:.1f} us per call (pack + kernel + slab reduce)")
-lib.frl_tcn_hot_bwd_variant(4)
+new = ops.tcn_block_bwd(x, dy, *args, dil, 8)
+torch.cuda.synchronize()
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+e0.record()
+for _ in range(10):
+    ops.tcn_block_bwd(x, dy, *args, dil, 8)
+e1.record()
+torch.cuda.synchronize()
+print(f"tcn_hot_bwd4: {e0.elapsed_time(e1) * 100:.1f} us per call (pack + kernel + slab reduce)")
 lib.frl_tcn_hot_force_generic_tiles(1)
-out[2] = ops.tcn_block_bwd(x, dy, *args, dil, 8)
+old = ops.tcn_block_bwd(x, dy, *args, dil, 8)
 lib.frl_tcn_hot_force_generic_tiles(0)
-for a, b in ((4, 3), (4, 2), (3, 2)):
-    for k in out[a]:
-        d = (out[a][k].double() - out[b][k].double()).abs()
-        ref = out[b][k].double().abs()
-        print(f"{a} vs {b} {k:8s} max {d.max().item() / ref.max().item():.2e}  mean {d.mean().item() / ref.mean().item():.2e}  "
-              f"differing {float((d > 0).double().mean()):.4f}")
+for k in new:
+    d = (new[k].double() - old[k].double()).abs()
+    ref = old[k].double().abs()
+    print(f"bwd4 vs round 1 {k:8s} max {d.max().item() / ref.max().item():.2e}  mean {d.mean().item() / ref.mean().item():.2e}  "
+          f"differing {float((d > 0).double().mean()):.4f}")

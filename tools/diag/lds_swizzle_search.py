@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bank-conflict model of the unpadded [pixel][128 B] LDS tiles of tcn_hot_bwd3 (gfx950 rules of MI355X_MICROARCH.md, section LDS)
+"""Bank-conflict model of the unpadded [pixel][128 B] LDS tiles of tcn_hot_bwd4 (gfx950 rules of MI355X_MICROARCH.md, section LDS)
 and a brute-force search over GF(2)-linear chunk swizzles  chunk' = chunk ^ f(pixel),  f = M * pixel_bits (3 x 6 bit matrix).
 
 Access patterns (lane l: px = l & 15, kc = l >> 4; wave (q, h)):
@@ -7,6 +7,8 @@ Access patterns (lane l: px = l & 15, kc = l >> 4; wave (q, h)):
   R1  ds_read_b128    row 16q+px, chunk 2kc+s                    (B operand rows, s = 0 / 1)
   T   ds_read_b64_tr  row 32ks+8kc+(r>>2)+4hi, 8-byte piece (r&3) of chunks 2cb, 2cb+1     (weight-gradient operands)
 Cost = LDS cycles per wave instruction (sum over lane groups of the worst bank multiplicity).
+The rows are modelled for a 64-pixel tile; the swizzle found only looks at the low four bits of the row, so it serves the kernel's
+32-pixel tiles unchanged.
 """
 import itertools
 import sys

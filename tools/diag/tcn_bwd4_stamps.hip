@@ -1,8 +1,8 @@
-// Diagnostic harness (not part of the product library): runs the hot TCN backward kernel with s_memtime stamps at its phase
-// boundaries and prints the median cycles per phase.  Build: tools/diag/build.sh ; run on the GPU box: tools/diag/tcn_bwd_stamps
-// build variants (tools/diag/build.sh): default (timing only), -DB3_STAMPS (phase stamps of tcn_hot_bwd3_kernel)
+// Diagnostic harness (not part of the product library): runs tcn_hot_bwd4_kernel with s_memtime stamps at its phase boundaries and
+// prints the mean cycles per phase.  Build: tools/diag/build.sh -> tcn_bwd4.bin (timing only), tcn_bwd4_stamps.bin (-DB4_STAMPS).
+// Usage: tcn_bwd4[_stamps].bin [dilation [priority mode [subgroup 0 share, 32nds]]] -- the kernel-variant argument that used to stand
+// second is gone, the two knobs of the stamps build moved down by one.
 #include "../../vq-vae_amd/csrc/tcn_hot.hip"
-#include "../../vq-vae_amd/csrc/tcn_hot_bwd3.hip"
 #include "../../vq-vae_amd/csrc/tcn_hot_bwd4.hip"
 #include "../../vq-vae_amd/csrc/frl_host.hip"
 #include <vector>
@@ -14,7 +14,6 @@
 int main(int argc, char** argv) {
   const int B = 256, T = 5, HW = 1024, C = 64;
   const int dil = argc > 1 ? atoi(argv[1]) : 1;
-  if (argc > 2) frl_tcn_hot_bwd_variant(atoi(argv[2]));            // 3: tcn_hot_bwd3_kernel, 4 (default): tcn_hot_bwd4_kernel
   const int64_t npix = (int64_t)B * HW, n = npix * T * C;
   std::mt19937 rng(1);
   std::normal_distribution<float> nd(0.f, 1.f);
@@ -43,13 +42,10 @@ int main(int argc, char** argv) {
   unsigned long long* dbg;
   const size_t ndbg = (size_t)256 * 4 * 16 * 8;
   CK(hipMalloc(&dbg, ndbg * 8)); CK(hipMemset(dbg, 0, ndbg * 8));
-#ifdef B3_STAMPS
-  CK(hipMemcpyToSymbol(HIP_SYMBOL(b3_dbg), &dbg, sizeof(dbg)));
-#endif
 #ifdef B4_STAMPS
   CK(hipMemcpyToSymbol(HIP_SYMBOL(b4_dbg), &dbg, sizeof(dbg)));
   {
-    int knob[2] = {argc > 3 ? atoi(argv[3]) : 0, argc > 4 ? atoi(argv[4]) : 16};
+    int knob[2] = {argc > 2 ? atoi(argv[2]) : 0, argc > 3 ? atoi(argv[3]) : 16};
     CK(hipMemcpyToSymbol(HIP_SYMBOL(b4_knob), knob, sizeof(knob)));
     printf("knobs: priority mode %d, subgroup 0 share %d/32\n", knob[0], knob[1]);
   }
@@ -62,7 +58,7 @@ int main(int argc, char** argv) {
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     printf("iter %d rc=%d  %.1f us (pack + bwd + slab reduce)\n", it, rc, ms * 1e3f);
   }
-#if !defined(B3_STAMPS) && !defined(B4_STAMPS)
+#ifndef B4_STAMPS
   return 0;
 #endif
   {

@@ -6,7 +6,7 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
-// fused TCN block backward (tcn_hot.hip, tcn_hot_bwd3.hip, tcn_hot_bwd4.hip, tcn_fused.hip): slab = [3][64][64] conv taps | [64][64] gate |
+// fused TCN block backward (tcn_hot.hip, tcn_hot_bwd4.hip, tcn_fused.hip): slab = [3][64][64] conv taps | [64][64] gate |
 // [64] d conv bias | [64] d gate bias | [64] d gamma | [64] d beta
 struct ThEpi {
   float *dWc, *dWg, *dbc, *dbg, *dgam, *dbet;

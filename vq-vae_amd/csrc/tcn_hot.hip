@@ -8,10 +8,16 @@
 // exact two-pass in-lane reduction over those accumulators, and the gate GEMM / sigmoid / blend read them in place.
 //
 //   forward : y = g * relu(n) + (1 - g) * x,  n = GN(conv(x) + b),  g = sigmoid(Wg n + bg)          (x read, y written: 2 x 128 B / (px,t))
-//   backward: ONE launch -> dx + every parameter gradient (tcn_hot_bwd2_kernel, 8 waves per workgroup with a channel-half split;
-//             the phase structure is described above the kernel).  Wave (q, h) owns rows [16q, 16q+16) x columns [32h, 32h+32) of the
-//             four 64x64 gradient matrices in registers for the whole kernel; per-workgroup float32 slabs are summed in a fixed order
-//             afterwards (bit-reproducible, no float atomics).
+//   backward: ONE launch -> dx + every parameter gradient; per-workgroup float32 slabs are summed in a fixed order afterwards
+//             (bit-reproducible, no float atomics).
+//
+// Kernels behind the C entry points at the end of this file:
+//   tcn_hot_fwd_kernel    forward of one block (frl_tcn_hot_fwd)
+//   tcn_chain_fwd_kernel  forward of the three blocks and the 1x1 phase head in one launch (frl_tcn_chain_fwd)
+//   tcn_hot_bwd2_kernel   backward with a Dropout1d mask, or when HW % 64 != 0 (pixel tiles may straddle samples): 8 waves per workgroup
+//                         with a channel-half split; wave (q, h) owns rows [16q, 16q+16) x columns [32h, 32h+32) of the four 64x64
+//                         gradient matrices in registers for the whole kernel (the phase structure is described above the kernel)
+//   tcn_hot_bwd4_kernel   backward of everything else, the measured configuration among it: tcn_hot_bwd4.hip
 #include "tcn_hot_common.hpp"
 
 // Diagnostic build only (tools/diag/tcn_bwd_stamps.hip defines TH_STAMPS): s_memtime stamps at the phase boundaries of the
@@ -367,9 +373,9 @@ __device__ __forceinline__ void th_put(bf16* tile, int prow, int kc, const Tile2
 // =============================================================================================================
 // backward, 8 waves per workgroup (two per SIMD): wave (q, h) owns the 16 pixels of quarter q and the channel half h of every
 // lane quarter (fragment h of the lane-quarter image = one 8-channel GroupNorm group per lane), i.e. half the per-lane state of
-// the 4-wave kernel above, so the compiler keeps everything in registers and two waves per SIMD hide each other's LDS / MFMA
-// latencies.  The GEMMs that contract over all 64 channels (gate, gate^T, conv^T) take the partner wave's half from the very
-// LDS tiles that are published for the weight-gradient GEMMs anyway:
+// a wave that owns all 64 channels of its pixels (as in the forward kernel), so the compiler keeps everything in registers and two
+// waves per SIMD hide each other's LDS / MFMA latencies.  The GEMMs that contract over all 64 channels (gate, gate^T, conv^T) take
+// the partner wave's half from the very LDS tiles that are published for the weight-gradient GEMMs anyway:
 //   S1  conv -> GroupNorm statistics -> n[t]                                  publish n[t]        | barrier A
 //   S2  gate GEMM, sigmoid, dgpre[t], dres[t] (parked in dx), relu path of dn  publish dgpre[t]    | barrier B
 //   S3  gate^T GEMM -> dn -> d gamma, d beta, GroupNorm backward -> dconv[t];  P2 gate weight gradient (rows 16q.., column half h)
@@ -786,6 +792,9 @@ static int th_launch_bwd(const void* x, const void* mask, const void* dy, const 
 }
 
 static int g_th_force_bwd2 = 0;
+// The staged route (tcn_hot_bwd4.hip) serves a shape when its tiles never straddle a sample and the test hook is off; a call with a
+// Dropout1d mask still goes to tcn_hot_bwd2_kernel.
+static bool th_bwd_staged_supported(int64_t npix, int HW) { return th_bwd4_supported(npix, HW) && !g_th_force_bwd2; }
 
 // Packed image of one block (layout of tcn_hot_pack_kernel): from the caller's image cache when one is active, else packed into `ws_pk`.
 static const frag8* th_packed(const float* conv_w, const float* gate_w, frag8* ws_pk, hipStream_t stream) {
@@ -806,10 +815,6 @@ extern "C" {
 
 // test hook: 1 routes every hot backward through the 8-wave kernel of this file (mask / ragged-tile path), 0 restores the dispatch
 int frl_tcn_hot_force_generic_tiles(int on) { const int was = g_th_force_bwd2; g_th_force_bwd2 = on; return was; }
-// 4 (default): tcn_hot_bwd4_kernel (two independent 4-wave subgroups per workgroup); 3: tcn_hot_bwd3_kernel (8 waves in lockstep).  Returns the
-// previous value; for A/B measurements and the parity tests of both kernels.
-static int g_th_bwd_variant = 4;
-int frl_tcn_hot_bwd_variant(int v) { const int was = g_th_bwd_variant; if (v == 3 || v == 4) g_th_bwd_variant = v; return was; }
 
 // 1 when the specialised kernels apply: bf16, 64 -> 64 channels, T = 5, 8 groups, identity residual, dilation 1 / 2 / 4
 int frl_tcn_hot_supported(int T, int Cin, int Cout, int G, int dilation, int has_proj, int dtype) {
@@ -817,7 +822,7 @@ int frl_tcn_hot_supported(int T, int Cin, int Cout, int G, int dilation, int has
 }
 
 // 1 when frl_tcn_hot_bwd accepts dx = NULL for this shape (the input needs no gradient: conv^T GEMM and dx store are skipped)
-int frl_tcn_hot_bwd_nodx_supported(int64_t npix, int HW) { return (th_bwd3_supported(npix, HW) && !g_th_force_bwd2) ? 1 : 0; }
+int frl_tcn_hot_bwd_nodx_supported(int64_t npix, int HW) { return th_bwd_staged_supported(npix, HW) ? 1 : 0; }
 
 size_t frl_tcn_hot_fwd_workspace_bytes(void) { return TH_PACK_BYTES; }
 size_t frl_tcn_hot_bwd_workspace_bytes(int64_t npix) { return (size_t)th_bwd_grid(npix) * TH_SLAB * sizeof(float) + 256 + TH_PACK_BYTES; }
@@ -898,12 +903,11 @@ int frl_tcn_hot_bwd(const void* x, const void* drop_mask, const void* dy, const 
   const frag8* pk = th_packed(conv_w, gate_w,
                               reinterpret_cast<frag8*>(reinterpret_cast<char*>(ws) + (((size_t)grid * TH_SLAB * sizeof(float) + 255) / 256) * 256), stream);
   int rc = -2;
-  if (dx == nullptr && !(drop_mask == nullptr && th_bwd3_supported(npix, HW) && !g_th_force_bwd2))
-    return frl_fail(-2, "tcn_hot_bwd: dx may be NULL (input without gradient) only on the tcn_hot_bwd3 route (no mask, HW % 64 == 0)");
-  if (drop_mask == nullptr && th_bwd3_supported(npix, HW) && !g_th_force_bwd2)      // the measured configuration: tcn_hot_bwd4.hip / tcn_hot_bwd3.hip
-    rc = (g_th_bwd_variant == 4 && th_bwd4_supported(npix, HW))
-             ? th_bwd4_launch(dilation, x, dy, pk, conv_b, gn_w, gn_b, gate_b, dx, slab, grid, npix, HW, eps, stream)
-             : th_bwd3_launch(dilation, x, dy, pk, conv_b, gn_w, gn_b, gate_b, dx, slab, grid, npix, HW, eps, stream);
+  const bool staged = drop_mask == nullptr && th_bwd_staged_supported(npix, HW);
+  if (dx == nullptr && !staged)
+    return frl_fail(-2, "tcn_hot_bwd: dx may be NULL (input without gradient) only on the staged route (no mask, HW % 64 == 0)");
+  if (staged)                                                       // the measured configuration: tcn_hot_bwd4.hip
+    rc = th_bwd4_launch(dilation, x, dy, pk, conv_b, gn_w, gn_b, gate_b, dx, slab, grid, npix, HW, eps, stream);
   else if (dilation == 1) rc = th_launch_bwd<1>(x, drop_mask, dy, pk, conv_b, gn_w, gn_b, gate_b, dx, slab, grid, npix, HW, eps, stream);
   else if (dilation == 2) rc = th_launch_bwd<2>(x, drop_mask, dy, pk, conv_b, gn_w, gn_b, gate_b, dx, slab, grid, npix, HW, eps, stream);
   else if (dilation == 4) rc = th_launch_bwd<4>(x, drop_mask, dy, pk, conv_b, gn_w, gn_b, gate_b, dx, slab, grid, npix, HW, eps, stream);
@@ -918,7 +922,7 @@ int frl_tcn_hot_bwd(const void* x, const void* drop_mask, const void* dy, const 
 // [B][5][HW][Ch] bf16 is the head's output gradient, head_w [Ch][64] float32; dy = dh head_w is formed inside the kernel (matrix cores) and
 // never written.  Same outputs as frl_tcn_hot_bwd.  Needs the two-subgroup kernel (no mask, HW % 64 == 0, dilation 4, dx != NULL).
 int frl_tcn_hot_bwd_head_supported(int64_t npix, int HW, int Ch) {
-  return (th_bwd4_supported(npix, HW) && !g_th_force_bwd2 && g_th_bwd_variant == 4 && Ch >= 4 && Ch <= 16 && (Ch & 3) == 0) ? 1 : 0;
+  return (th_bwd_staged_supported(npix, HW) && Ch >= 4 && Ch <= 16 && (Ch & 3) == 0) ? 1 : 0;
 }
 size_t frl_tcn_hot_bwd_head_workspace_bytes(int64_t npix) { return frl_tcn_hot_bwd_workspace_bytes(npix) + 4096; }
 int frl_tcn_hot_bwd_head(const void* x, const void* dh, const float* head_w, int Ch, const float* conv_w, const float* conv_b, const float* gn_w,

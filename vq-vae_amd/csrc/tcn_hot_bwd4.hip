@@ -3,19 +3,29 @@
 // Backward of the hot-configuration GatedResidualBlock (frl/models/tcn.py:78-111; bf16, 64 -> 64 channels, T = 5, 8-channel GroupNorm
 // groups, identity residual, dilation 1 / 2 / 4, no Dropout1d mask, HW % 64 == 0): ONE launch -> dx and all six parameter gradients.
 //
-// Same math, data placement and phase sequence as tcn_hot_bwd3_kernel (tcn_hot_bwd3.hip), re-cut so that the units of a SIMD stop taking
-// turns: the workgroup's 8 waves are TWO independent subgroups of 4 waves (one wave per SIMD each), every subgroup walks its own
+// Same math and slab layout as tcn_hot_bwd2_kernel (tcn_hot.hip); what differs is where the data lives, so that nothing spills and
+// nothing takes a second trip through HBM (algorithmic traffic: x and dy read once, dx written once = 3 x 128 B per (pixel, t)), and
+// how the workgroup is cut: its 8 waves are TWO independent subgroups of 4 waves (one wave per SIMD each), every subgroup walks its own
 // 32-pixel tiles (wave (q, h) of a subgroup owns the 16 pixels of half q and the channel half h of every lane quarter) and synchronises
-// only with itself, through a counter in LDS instead of s_barrier.  In tcn_hot_bwd3 all 8 waves sit in the same phase between two
-// workgroup barriers, so the two waves of a SIMD want the matrix pipe, the vector ALU or the LDS at the same moment and each unit idles
-// while another one is the bottleneck (~7.5 k cycles of each per 64 pixels, ~30 k cycles in total); here the two waves of a SIMD belong
-// to different subgroups and drift apart, one streaming MFMAs while the other is in the GroupNorm / sigmoid chain.
-//   * LDS: the ONE packed weight image (32 KB) and the parameter table are shared; each subgroup has its own three 20 KB tile buffers
-//     X | N | A (x by LDS-DMA one tile ahead, chunk swizzle and transposing reads exactly as in tcn_hot_bwd3: the swizzle only looks at
-//     the low four bits of the pixel row).
+// only with itself, through a counter in LDS instead of s_barrier.  The round-2 form of this kernel kept all 8 waves in one phase over
+// 64-pixel tiles, between two workgroup barriers, so the two waves of a SIMD wanted the matrix pipe, the vector ALU or the LDS at the
+// same moment and each unit idled while another one was the bottleneck (~7.5 k cycles of each per 64 pixels, ~30 k cycles in total);
+// here the two waves of a SIMD belong to different subgroups and drift apart, one streaming MFMAs while the other is in the GroupNorm /
+// sigmoid chain.
+//   * x[t] of a tile is brought in by LDS-DMA (global_load_lds_dwordx4) and STAYS in LDS for the whole tile: conv operands, the
+//     residual and the weight-gradient operand are read from there, no register copy of x exists.  The DMA of the subgroup's next tile
+//     is issued as soon as this tile's n[t] buffer is free (after barrier C) and lands behind the conv^T / weight-gradient phases.
+//   * LDS: the ONE packed weight image (conv taps + gate, 32 KB) and the parameter table are shared; the transposed operands of the
+//     gate^T / conv^T GEMMs are fetched from the same image with ds_read_b64_tr_b16 (a 4 x 16 block of it IS a transposed fragment), so
+//     no second image is kept.  Each subgroup has its own three unpadded 20 KB tile buffers [t][32 px][128 B]: X | N | A, with X and N
+//     swapping roles every tile; a chunk swizzle chunk' = chunk ^ f(px) (f found by tools/diag/lds_swizzle_search.py; it only looks at
+//     the low four bits of the pixel row) makes the 16-byte row accesses AND the transposing reads bank-conflict free without padding
+//     (the DMA writes LDS linearly, so the swizzle sits on its source address).
+//   * dres = dy (1 - g) is carried in registers instead of being parked in dx: dy g is kept (packed bf16) and subtracted from dy at
+//     the dx store.
 //   * weight gradients contract over the 32 pixels of the subgroup's tile = ONE 16x16x32 MFMA k-step; a wave accumulates a 32 x 32
-//     block of each of the four matrices (16 accumulator tiles instead of 8) -- the two subgroups' sums are added through LDS in a
-//     fixed order before the slab is written, so the slab layout and the reduction are those of tcn_hot_bwd3.
+//     block of each of the four matrices in registers for the whole kernel (16 accumulator tiles) -- the two subgroups' sums are added
+//     through LDS in a fixed order before the slab is written, so slab layout and reduction are those of tcn_hot_bwd2_kernel.
 //
 //   E' wait for the DMA of x, subgroup barrier   conv -> GroupNorm statistics -> n[t]            publish n[t] (own 8 channels)   | A
 //   S2 gate GEMM, sigmoid, dgpre[t], dres[t] (registers), relu path of dn                        publish dgpre[t]                | B
@@ -38,7 +48,7 @@
 // the weight gradients depend on timing), and it is NOT half: when both waves of a SIMD are ready the sequencer issues from the older
 // one, so subgroup 0 (waves 0-3) runs a tile in ~22 k cycles and subgroup 1 in ~31 k while both are busy (s_setprio on subgroup 1 does
 // not change that); with 16/32 subgroup 0 finished its tiles at 76 % of the workgroup's lifetime.  19/32 lets both end together on the
-// measured configuration (tools/diag/tcn_bwd3_stamps.hip: workgroup lifetime 459 k -> 425 k cycles; 18: 434 k, 20: 442 k).
+// measured configuration (tools/diag/tcn_bwd4_stamps.hip: workgroup lifetime 459 k -> 425 k cycles; 18: 434 k, 20: 442 k).
 #define B4_SHARE0 19
 
 // chunk swizzle of the tile buffers: 16-byte chunk c of pixel row r is stored at chunk position c ^ b4_swz(r)
@@ -116,7 +126,7 @@ __device__ __forceinline__ void b4_sync(unsigned* bar, unsigned& gen, int lane) 
 #define B4_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); b4_sync(bar, bgen, lane); asm volatile("" ::: "memory"); } while (0)
 #define B4_BARRIER_ALL() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); b4_sync(bar, bgen, lane); asm volatile("" ::: "memory"); } while (0)
 
-// Diagnostic build only (tools/diag/tcn_bwd3_stamps.hip defines B4_STAMPS): s_memtime stamps at the phase boundaries, accumulated in the
+// Diagnostic build only (tools/diag/tcn_bwd4_stamps.hip defines B4_STAMPS): s_memtime stamps at the phase boundaries, accumulated in the
 // spare LDS behind the d gamma / d beta slots and written to a buffer nothing else reads.  The product library never defines it.
 #ifdef B4_STAMPS
 __device__ unsigned long long* b4_dbg;

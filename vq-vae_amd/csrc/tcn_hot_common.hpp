@@ -1,5 +1,6 @@
-// Shared pieces of the hot-configuration GatedResidualBlock kernels (tcn_hot.hip: forward + 8-wave backward with a Dropout1d mask or a
-// ragged pixel count; tcn_hot_bwd3.hip: the backward of the measured configuration).  Reference: frl/models/tcn.py:78-111.
+// Shared pieces of the hot-configuration GatedResidualBlock kernels (tcn_hot.hip: per-block and chain forward, the 8-wave backward with a
+// Dropout1d mask or a ragged pixel count; tcn_hot_bwd4.hip: the backward of everything else, the measured configuration among it).
+// Reference: frl/models/tcn.py:78-111.
 #pragma once
 #include "tcn_common.hpp"
 #include "frl_host.hpp"
@@ -33,11 +34,8 @@ static inline unsigned th_bwd_grid(int64_t npix) {
   return (unsigned)g;
 }
 
-// tcn_hot_bwd3.hip: backward without mask for HW % 64 == 0 (64-pixel tiles never straddle a sample); same slab layout as tcn_hot_bwd2_kernel
-bool th_bwd3_supported(int64_t npix, int HW);
-int th_bwd3_launch(int dilation, const void* x, const void* dy, const frag8* pk, const float* bc, const float* gw, const float* gb, const float* bg,
-                   void* dx, float* slab, unsigned grid, int64_t npix, int HW, float eps, hipStream_t st);
-// tcn_hot_bwd4.hip: the same backward cut into two independent 4-wave subgroups per workgroup (32-pixel tiles); same conditions and slabs
+// tcn_hot_bwd4.hip: backward without mask for HW % 64 == 0 (tiles never straddle a sample), two independent 4-wave subgroups per workgroup over
+// 32-pixel tiles; same slab layout as tcn_hot_bwd2_kernel.  whp != NULL: the variant that forms dy from the phase head's output gradient.
 bool th_bwd4_supported(int64_t npix, int HW);
 int th_bwd4_launch(int dilation, const void* x, const void* dy, const frag8* pk, const float* bc, const float* gw, const float* gb, const float* bg,
                    void* dx, float* slab, unsigned grid, int64_t npix, int HW, float eps, hipStream_t st, const frag8* whp = nullptr, int chd = 0);

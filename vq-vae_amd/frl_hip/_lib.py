@@ -130,7 +130,6 @@ SIGNATURES = {
     "frl_tcn_hot_fwd": (c_int, [P, P, P, P, P, P, P, P, P, L, I, I, F, P, S, P]),
     "frl_tcn_hot_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, F, P, S, P]),
     "frl_tcn_hot_force_generic_tiles": (c_int, [I]),
-    "frl_tcn_hot_bwd_variant": (c_int, [I]),
     "frl_decoder_mse_bwd_subgroups": (c_int, [I]),
     "frl_tcn_hot_bwd4_share": (c_int, [I, I]),
     "frl_tcn_chain_static_tiles": (c_int, [I]),

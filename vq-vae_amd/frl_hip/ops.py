@@ -992,7 +992,7 @@ def smooth_heads_bwd(d_smoothed, x, feat, wa, ba, wb, bb, coarse_dilation: int, 
 
 
 # ----------------------------------------------------------------------------------------------
-# fused TCN block (csrc/tcn_fwd.hip, tcn_bwd.hip); x [B,T,HW..,Cin]
+# fused TCN block (csrc/tcn_fwd.hip, tcn_bwd.hip; hot configuration: tcn_hot.hip, tcn_hot_bwd4.hip); x [B,T,HW..,Cin]
 # ----------------------------------------------------------------------------------------------
 def tcn_hot_supported(x: torch.Tensor, cin: int, cout: int, groups: int, dilation: int, has_projection: bool) -> bool:
     """True when the block on x [B,T,..,Cin] runs on the specialised `tcn_hot_*` kernels (the only ones that take a Dropout1d mask)."""
