@@ -466,6 +466,35 @@ int frl_vicreg_fwd(const void* x, int64_t N, int D, int dtype, float variance_we
 int frl_vicreg_bwd(const void* x, const float* cov, const float* centre, const float* g3, int64_t N, int D, int dtype, float variance_weight,
                    float covariance_weight, float variance_target, float eps, void* dx, frl_stream_t stream);
 
+/* ---- soft-neighbourhood matching loss (csrc/soft_neighborhood.hip) -----------------------------------------------------------
+ * soft_neighborhood_matching_loss of frl/losses/soft_neighborhood.py:46-208 (the two terms of phase_neighborhood_loss,
+ * frl/losses/phase_neighborhood.py:458-630): per pair b and row t over the unmasked entries t' only, lp = log_softmax(-d_ref / tau_ref),
+ * lq = log_softmax(-d_learned / tau_learned), kl = sum p (lp - lq); rows with fewer than min_valid unmasked entries are skipped,
+ * L_b = mean kl over the rows_b contributing rows, loss = sum w_b L_b / sum w_b over the pairs with rows_b > 0 (0 when there is none or
+ * the weights sum to 0).  The temperatures are passed as reciprocals.  pairstat [B][6] = L_b, rows_b, sum of the contributing rows'
+ * unmasked counts, sum H(p), sum H(q), sum kl;  out2 [2] = loss, sum_w;  stats [8] doubles = loss, sum_w, active pairs, contributing
+ * rows, sum of unmasked counts, sum H(p), sum H(q), 0.  Fixed reduction order, no float atomics: both forms are bit-reproducible.
+ * Matrix form: d_ref, d_learned [B][M][M] f32, mask [B][M][M] bytes, weights [B] or NULL, any M >= 1; coef [B][M][M] (NULL = no gradient
+ * wanted) = (p - q) / tau_learned, and frl_soft_nbr_bwd gives grad = gup[0] * w_b / (sum_w * rows_b) * coef (gup: device float).
+ * Gathered form: the blocks are formed on chip from rows of ref [R][C] f32 and emb [R][D] (dtype 0 = float32, 1 = bfloat16):
+ * d_ref[t][t'] = |ref[ref_rows_a[b][t]] - ref[ref_rows_b[b][t']]|_2, likewise emb; mask = t < K_b and t' < K_b (lengths [B] int64), minus
+ * the diagonal when exclude_diagonal.  The four [B][M] int64 index arrays must lie in [0, R).  M <= 32, C <= 256, D <= 256.
+ * frl_soft_nbr_gathered_bwd writes grad_rows [2][B][M][D] f32 (role a, then role b; zero where the distance is zero, torch.cdist's
+ * convention, and beyond K_b) for frl_segment_sum_rows to fold into d emb. */
+int frl_soft_nbr_fwd(const float* d_ref, const float* d_learned, const unsigned char* mask, const float* weights, int64_t B, int M,
+                     float inv_tau_ref, float inv_tau_learned, int min_valid, float* pairstat, float* coef, float* out2, double* stats,
+                     frl_stream_t stream);
+int frl_soft_nbr_bwd(const float* coef, const float* pairstat, const float* weights, const float* out2, const float* gup, int64_t B, int M,
+                     float* grad, frl_stream_t stream);
+int frl_soft_nbr_gathered_fwd(const float* ref, int C, const void* emb, int D, int emb_dtype, const int64_t* ref_rows_a, const int64_t* ref_rows_b,
+                              const int64_t* emb_rows_a, const int64_t* emb_rows_b, const int64_t* lengths, const float* weights, int64_t B, int M,
+                              int exclude_diagonal, float inv_tau_ref, float inv_tau_learned, int min_valid, float* pairstat, float* out2,
+                              double* stats, frl_stream_t stream);
+int frl_soft_nbr_gathered_bwd(const float* ref, int C, const void* emb, int D, int emb_dtype, const int64_t* ref_rows_a, const int64_t* ref_rows_b,
+                              const int64_t* emb_rows_a, const int64_t* emb_rows_b, const int64_t* lengths, const float* weights, int64_t B, int M,
+                              int exclude_diagonal, float inv_tau_ref, float inv_tau_learned, int min_valid, const float* pairstat,
+                              const float* out2, const float* gup, float* grad_rows, frl_stream_t stream);
+
 /* ---- code-map decoding (csrc/codes.hip) --------------------------------------------------------------------------------------
  * frl_decode_codes: out[p][:] = table[idx[p]][:] for a decoded-code table [K][F] (dtype 0 = float32, 1 = bfloat16; the VQ-VAE decoder
  * applied to the K codebook rows), idx [P] int32.  Indices in [-K, 0) wrap to idx + K; any other out-of-range index is clamped into

@@ -152,6 +152,10 @@ SIGNATURES = {
     "frl_vicreg_workspace_bytes": (S, [L, I]),
     "frl_vicreg_fwd": (c_int, [P, L, I, I, F, F, F, F, P, P, P, P, S, P]),
     "frl_vicreg_bwd": (c_int, [P, P, P, P, L, I, I, F, F, F, F, P, P]),
+    "frl_soft_nbr_fwd": (c_int, [P, P, P, P, L, I, F, F, I, P, P, P, P, P]),
+    "frl_soft_nbr_bwd": (c_int, [P, P, P, P, P, L, I, P, P]),
+    "frl_soft_nbr_gathered_fwd": (c_int, [P, I, P, I, I, P, P, P, P, P, P, L, I, I, F, F, I, P, P, P, P]),
+    "frl_soft_nbr_gathered_bwd": (c_int, [P, I, P, I, I, P, P, P, P, P, P, L, I, I, F, F, I, P, P, P, P, P]),
 }
 
 

@@ -1,3 +1,5 @@
 from .pairs import pairs_mutual_knn_chunked  # noqa: F401
 from .contrastive import contrastive_loss  # noqa: F401
 from .variance_covariance import variance_covariance_loss, variance_loss, covariance_loss  # noqa: F401
+from .soft_neighborhood import (soft_neighborhood_matching_loss, soft_neighborhood_loss_gathered, phase_alignment,  # noqa: F401
+                                phase_neighborhood_loss)

@@ -1387,3 +1387,129 @@ def vicreg_bwd(x: torch.Tensor, cov: torch.Tensor, centre: torch.Tensor, g3: tor
     check(_lib.load().frl_vicreg_bwd(_p(x), _p(cov), _p(centre), _p(g3), n, d, _dt(x), float(variance_weight), float(covariance_weight),
                                      float(variance_target), float(eps), _p(dx), _stream()), "frl_vicreg_bwd")
     return dx
+
+
+# ----------------------------------------------------------------------------------------------
+# soft-neighbourhood matching loss (csrc/soft_neighborhood.hip)
+# ----------------------------------------------------------------------------------------------
+SOFT_NBR_MAX_M, SOFT_NBR_MAX_WIDTH = 32, 256
+
+
+def _chk_soft_nbr(name: str, tau_ref: float, tau_learned: float, min_valid_per_row: int):
+    if int(min_valid_per_row) < 2:
+        raise ValueError(f"min_valid_per_row must be >= 2, got {min_valid_per_row}")
+    if not (tau_ref > 0 and tau_learned > 0):
+        raise ValueError(f"{name}: temperatures must be positive, got tau_ref={tau_ref} tau_learned={tau_learned}")
+
+
+def _soft_nbr_weights(weights: Optional[torch.Tensor], b: int, device, name: str):
+    if weights is None:
+        return None
+    if weights.dtype != torch.float32 or not weights.is_contiguous() or weights.shape != (b,) or weights.device != device:
+        raise ValueError(f"{name}: pair weights must be a contiguous float32 [{b}] tensor on the device of the inputs")
+    return weights
+
+
+def _soft_nbr_outputs(b: int, device):
+    return (torch.empty(b, 6, dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
+            torch.empty(8, dtype=torch.float64, device=device))
+
+
+@_timed("soft_nbr_fwd")
+def soft_nbr_fwd(d_reference: torch.Tensor, d_learned: torch.Tensor, mask: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                 tau_ref: float = 1.0, tau_learned: float = 1.0, min_valid_per_row: int = 2, want_coef: bool = True):
+    """d_reference, d_learned [B, M, M] float32, mask [B, M, M] bool, weights [B] float32 or None -> (out2 f32 [2] = loss, sum of the
+    active pairs' weights; stats f64 [8] = loss, sum_w, active pairs, contributing rows, sum of their unmasked counts, sum H(p), sum H(q), 0;
+    pairstat f32 [B, 6] = L_b, rows_b, ...; coef f32 [B, M, M] = (p - q) / tau_learned, None unless want_coef)."""
+    _chk_soft_nbr("soft_nbr_fwd", tau_ref, tau_learned, min_valid_per_row)
+    if not (d_reference.is_cuda and d_learned.is_cuda and mask.is_cuda):
+        raise _lib.FrlHipError("soft_nbr_fwd: tensors must live on the GPU (no CPU fallback)")
+    if d_reference.dim() != 3 or d_reference.shape[1] != d_reference.shape[2] or d_reference.shape[0] < 1 or d_reference.shape[1] < 1:
+        raise ValueError(f"soft_nbr_fwd: expected [B >= 1, M >= 1, M] distances, got {tuple(d_reference.shape)}")
+    for t, dt, name in ((d_reference, torch.float32, "d_reference"), (d_learned, torch.float32, "d_learned"), (mask, torch.bool, "mask")):
+        if t.dtype != dt or t.shape != d_reference.shape or not t.is_contiguous() or t.device != d_reference.device:
+            raise ValueError(f"soft_nbr_fwd: {name} must be a contiguous {dt} {tuple(d_reference.shape)} tensor on {d_reference.device}")
+    b, m, _ = d_reference.shape
+    weights = _soft_nbr_weights(weights, b, d_reference.device, "soft_nbr_fwd")
+    pairstat, out2, stats = _soft_nbr_outputs(b, d_reference.device)
+    coef = torch.empty_like(d_learned) if want_coef else None
+    check(_lib.load().frl_soft_nbr_fwd(_p(d_reference), _p(d_learned), _p(mask), _p(weights), b, m, 1.0 / float(tau_ref), 1.0 / float(tau_learned),
+                                       int(min_valid_per_row), _p(pairstat), _p(coef), _p(out2), _p(stats), _stream()), "frl_soft_nbr_fwd")
+    return out2, stats, pairstat, coef
+
+
+@_timed("soft_nbr_bwd")
+def soft_nbr_bwd(coef: torch.Tensor, pairstat: torch.Tensor, weights: Optional[torch.Tensor], out2: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """d loss / d d_learned [B, M, M] = g[0] * w_b / (sum_w * rows_b) * coef for the outputs of soft_nbr_fwd; g: float32 [1] on the device."""
+    if not coef.is_cuda:
+        raise _lib.FrlHipError("soft_nbr_bwd: tensors must live on the GPU (no CPU fallback)")
+    b, m, _ = coef.shape
+    for t, shape, name in ((coef, (b, m, m), "coef"), (pairstat, (b, 6), "pairstat"), (out2, (2,), "out2"), (g, (1,), "g")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != coef.device:
+            raise ValueError(f"soft_nbr_bwd: {name} must be a contiguous float32 {shape} tensor on the device of coef")
+    weights = _soft_nbr_weights(weights, b, coef.device, "soft_nbr_bwd")
+    grad = torch.empty_like(coef)
+    check(_lib.load().frl_soft_nbr_bwd(_p(coef), _p(pairstat), _p(weights), _p(out2), _p(g), b, m, _p(grad), _stream()), "frl_soft_nbr_bwd")
+    return grad
+
+
+def _chk_soft_nbr_gathered(name: str, ref, emb, rows, lengths, checked: bool):
+    """Shape limits first (they hold on any device), then the device, then the layouts -> (B, M, rows [4, B, M] inside [0, R))."""
+    if ref.dim() != 2 or emb.dim() != 2 or ref.shape[0] != emb.shape[0]:
+        raise ValueError(f"{name}: expected ref [R, C] and emb [R, D], got {tuple(ref.shape)} and {tuple(emb.shape)}")
+    if rows.dim() != 3 or rows.shape[0] != 4:
+        raise ValueError(f"{name}: the row indices come stacked as [4, B, M] (ref a, ref b, emb a, emb b), got {tuple(rows.shape)}")
+    _, b, m = rows.shape
+    if m > SOFT_NBR_MAX_M:
+        raise ValueError(f"{name}: the gathered form supports M <= {SOFT_NBR_MAX_M} positions per pair, got M = {m}")
+    if ref.shape[1] > SOFT_NBR_MAX_WIDTH or emb.shape[1] > SOFT_NBR_MAX_WIDTH:
+        raise ValueError(f"{name}: the gathered form supports C <= {SOFT_NBR_MAX_WIDTH} and D <= {SOFT_NBR_MAX_WIDTH}, got C = {ref.shape[1]}, "
+                         f"D = {emb.shape[1]}")
+    if not (ref.is_cuda and emb.is_cuda and rows.is_cuda and lengths.is_cuda):
+        raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+    if b < 1 or m < 1 or ref.shape[0] < 1 or ref.shape[1] < 1 or emb.shape[1] < 1:
+        raise ValueError(f"{name}: needs at least one pair, position, row and column")
+    if ref.dtype != torch.float32 or not ref.is_contiguous() or emb.dtype not in (torch.float32, torch.bfloat16) or not emb.is_contiguous():
+        raise ValueError(f"{name}: ref must be contiguous float32 rows and emb contiguous float32 or bfloat16 rows")
+    if rows.dtype != torch.int64 or not rows.is_contiguous() or lengths.dtype != torch.int64 or not lengths.is_contiguous() or lengths.shape != (b,):
+        raise ValueError(f"{name}: row indices [4, {b}, {m}] and lengths [{b}] must be contiguous int64")
+    if not checked:
+        rows = sanitize_indices(rows, ref.shape[0], name + ": row indices")
+    return b, m, rows
+
+
+@_timed("soft_nbr_gathered_fwd")
+def soft_nbr_gathered_fwd(ref: torch.Tensor, emb: torch.Tensor, rows: torch.Tensor, lengths: torch.Tensor, exclude_diagonal: bool,
+                          weights: Optional[torch.Tensor] = None, tau_ref: float = 1.0, tau_learned: float = 1.0, min_valid_per_row: int = 2,
+                          checked: bool = False):
+    """ref [R, C] float32, emb [R, D] float32 | bfloat16, rows [4, B, M] int64 (ref a, ref b, emb a, emb b), lengths [B] int64 ->
+    (out2, stats, pairstat as soft_nbr_fwd, rows sanitised into [0, R)).  M <= 32, C <= 256, D <= 256."""
+    _chk_soft_nbr("soft_nbr_gathered_fwd", tau_ref, tau_learned, min_valid_per_row)
+    b, m, rows = _chk_soft_nbr_gathered("soft_nbr_gathered_fwd", ref, emb, rows, lengths, checked)
+    weights = _soft_nbr_weights(weights, b, ref.device, "soft_nbr_gathered_fwd")
+    pairstat, out2, stats = _soft_nbr_outputs(b, ref.device)
+    check(_lib.load().frl_soft_nbr_gathered_fwd(_p(ref), ref.shape[1], _p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(rows[2]),
+                                                _p(rows[3]), _p(lengths), _p(weights), b, m, int(bool(exclude_diagonal)), 1.0 / float(tau_ref),
+                                                1.0 / float(tau_learned), int(min_valid_per_row), _p(pairstat), _p(out2), _p(stats), _stream()),
+          "frl_soft_nbr_gathered_fwd")
+    return out2, stats, pairstat, rows
+
+
+@_timed("soft_nbr_gathered_bwd")
+def soft_nbr_gathered_bwd(ref: torch.Tensor, emb: torch.Tensor, rows: torch.Tensor, lengths: torch.Tensor, exclude_diagonal: bool,
+                          weights: Optional[torch.Tensor], tau_ref: float, tau_learned: float, min_valid_per_row: int, pairstat: torch.Tensor,
+                          out2: torch.Tensor, g: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """Gradient rows float32 [2, B, M, D] (role a = rows[2], then role b = rows[3]) for the outputs of soft_nbr_gathered_fwd; fold them
+    into d emb with segment_sum_rows.  g: float32 [1] on the device."""
+    _chk_soft_nbr("soft_nbr_gathered_bwd", tau_ref, tau_learned, min_valid_per_row)
+    b, m, rows = _chk_soft_nbr_gathered("soft_nbr_gathered_bwd", ref, emb, rows, lengths, checked)
+    for t, shape, name in ((pairstat, (b, 6), "pairstat"), (out2, (2,), "out2"), (g, (1,), "g")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != ref.device:
+            raise ValueError(f"soft_nbr_gathered_bwd: {name} must be a contiguous float32 {shape} tensor on the device of ref")
+    weights = _soft_nbr_weights(weights, b, ref.device, "soft_nbr_gathered_bwd")
+    grows = torch.empty(2, b, m, emb.shape[1], dtype=torch.float32, device=ref.device)
+    check(_lib.load().frl_soft_nbr_gathered_bwd(_p(ref), ref.shape[1], _p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(rows[2]),
+                                                _p(rows[3]), _p(lengths), _p(weights), b, m, int(bool(exclude_diagonal)), 1.0 / float(tau_ref),
+                                                1.0 / float(tau_learned), int(min_valid_per_row), _p(pairstat), _p(out2), _p(g), _p(grows),
+                                                _stream()), "frl_soft_nbr_gathered_bwd")
+    return grows
