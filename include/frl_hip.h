@@ -289,6 +289,12 @@ int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* co
                       const float* head_b, void* y1, void* y2, void* y3, void* h, int64_t npix, int HW, int Ch, float eps, void* ws,
                       size_t ws_bytes, frl_stream_t stream);
 /* y1 = y2 = y3 = NULL: inference variant of the same launch (h only, bitwise the same h); a mix of NULL and non-NULL is an argument error. */
+/* The same launch with the side output xt [B][HW][64] bf16 = mean over t of x, bit for bit what frl_mean_time_fwd writes: the tile is
+ * in registers there anyway, so the train step needs no separate pass over it.  xt = NULL: frl_tcn_chain_fwd. */
+int frl_tcn_chain_fwd_xt(const void* x, const float* const* conv_w, const float* const* conv_b, const float* const* gn_w,
+                         const float* const* gn_b, const float* const* gate_w, const float* const* gate_b, const float* head_w,
+                         const float* head_b, void* y1, void* y2, void* y3, void* h, void* xt, int64_t npix, int HW, int Ch, float eps,
+                         void* ws, size_t ws_bytes, frl_stream_t stream);
 /* The last block of the phase encoder together with the backward-data of the 1x1 phase head behind it (representation.py:169): `dh`
  * [B][5][HW][Ch] bf16 is the head's output gradient, head_w [Ch][64] float32, Ch in {4, 8, 12, 16}; dy = dh head_w is formed inside the
  * kernel on the matrix cores (float32, never written).  Same outputs as frl_tcn_hot_bwd; needs the two-subgroup kernel: no mask,

@@ -257,6 +257,7 @@ struct ThChainArgs {
   const float* bh;                                                 // head bias [Ch]
   bf16* y[3];
   bf16* h;
+  bf16* xt;                                                        // optional side output [B][HW][64]: the time mean of x (NULL: not written)
 };
 
 #define THC_IMG (32 * 64)                                          // fragments of one block's forward image (conv taps + gate)
@@ -287,7 +288,10 @@ __global__ __launch_bounds__(512, 2) void tcn_chain_fwd_kernel(const bf16* __res
   // while both are busy (measured in tcn_hot_bwd4: profiles/r03_tcn_bwd_stamps.md) and a static split leaves the older waves idle at the
   // end.  The forward accumulates nothing across tiles, so which wave computes a tile does not change a bit of the result.
   int* tctr = reinterpret_cast<int*>(tab + 3 * 256 + 16);
-  if (tid == 0) *tctr = 8;
+  if (tid == 0) {
+    *tctr = 8;
+    *reinterpret_cast<bf16**>(tctr + 2) = a.xt;                    // re-read from LDS per tile: two scalar registers less across the block bodies
+  }
   __syncthreads();
   const int64_t ntile = (npix + 15) >> 4;
   const int64_t tstep = (int64_t)gridDim.x * 8;
@@ -316,6 +320,25 @@ __global__ __launch_bounds__(512, 2) void tcn_chain_fwd_kernel(const bf16* __res
     int lw = lane, z0 = 0;
     asm volatile("" : "+v"(lw), "+s"(z0));                        // opaque per tile: neither the weight fragments nor the 3 x 48 per-channel
     const float* tb_ = tab + z0;                                  // constants are hoisted out of the tile loop into registers
+    bf16* const xtp = *reinterpret_cast<bf16* const*>(tctr + 2 + z0);
+    {
+      // time mean of the rows already in registers, in mean_time_kernel's arithmetic (elementwise.hip: float32 sum from 0 in order
+      // t = 0 .. 4, one multiply by 1 / T, RNE to bf16): bit for bit the tensor frl_mean_time_fwd writes, without its pass over the tile
+      // (computed whether or not it is stored -- ~100 VALU operations beside three block bodies -- so that only the store is conditional:
+      // a branch around the sum, or the pointer as a kernel argument, cost 4-12 B of scratch across the block bodies)
+      float s[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) s[j] = 0.f;
+#pragma unroll
+      for (int t = 0; t < TH_T; ++t)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) s[j] += th_elem(x[t], j);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) s[j] *= 1.f / (float)TH_T;
+      // (address from the per-tile opaque lane id: nothing lane-dependent of it stays live across the block bodies)
+      if (valid && xtp != nullptr) th_store(xtp + tile * 1024 + ((unsigned)(lw & 15) * 64u + (unsigned)(lw >> 4) * 16u), th_pack(s));
+      __builtin_amdgcn_sched_barrier(0);                           // (the sum is dead before the first block body starts)
+    }
     th_block_regs<1>(x, wl, wl + 24 * 64, tb_, lw, kc, eps);
     if (KEEP && valid) {
 #pragma unroll
@@ -847,13 +870,15 @@ int frl_tcn_hot_fwd(const void* x, const void* drop_mask, const float* conv_w, c
 // The dense phase chain forward in one launch: x [B][5][HW][64] -> y1, y2, y3 (outputs of the blocks with dilation 1, 2, 4; same shape) and
 // h [B][5][HW][Ch] = head_w y3 + head_b (Ch <= 16, a multiple of 4).  Block parameters as in frl_tcn_hot_fwd, one set per block.
 // y1 = y2 = y3 = NULL selects the inference variant (h only, same arithmetic); a mix of NULL and non-NULL outputs is an argument error.
+// frl_tcn_chain_fwd_xt: the same launch with the side output xt [B][HW][64] = mean over t of x, bit for bit what frl_mean_time_fwd
+// writes (xt = NULL: no side output, which is frl_tcn_chain_fwd).
 size_t frl_tcn_chain_fwd_workspace_bytes(void) { return 3 * TH_PACK_BYTES + 4096; }
 // A/B hook: 1 = every wave walks its own fixed tile sequence (the round-3 first version), 0 (default) = tiles handed out by an LDS counter
 static int g_thc_static = 0;
 int frl_tcn_chain_static_tiles(int on) { const int was = g_thc_static; g_thc_static = on ? 1 : 0; return was; }
-int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* const* conv_b, const float* const* gn_w, const float* const* gn_b,
-                      const float* const* gate_w, const float* const* gate_b, const float* head_w, const float* head_b, void* y1, void* y2, void* y3,
-                      void* h, int64_t npix, int HW, int Ch, float eps, void* ws, size_t ws_bytes, hipStream_t stream) {
+int frl_tcn_chain_fwd_xt(const void* x, const float* const* conv_w, const float* const* conv_b, const float* const* gn_w, const float* const* gn_b,
+                         const float* const* gate_w, const float* const* gate_b, const float* head_w, const float* head_b, void* y1, void* y2, void* y3,
+                         void* h, void* xt, int64_t npix, int HW, int Ch, float eps, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (npix <= 0 || HW <= 0) return frl_fail(-2, "tcn_chain_fwd: empty input");
   if (Ch < 4 || Ch > 16 || (Ch & 3)) return frl_fail(-2, "tcn_chain_fwd: head width must be 4, 8, 12 or 16");
   if (ws == nullptr || ws_bytes < frl_tcn_chain_fwd_workspace_bytes()) return frl_fail(-4, "tcn_chain_fwd: workspace too small");
@@ -877,6 +902,7 @@ int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* co
   }
   a.bh = head_b;
   a.y[0] = (bf16*)y1; a.y[1] = (bf16*)y2; a.y[2] = (bf16*)y3; a.h = (bf16*)h;
+  a.xt = (bf16*)xt;
   int64_t g = ((npix + 15) / 16 + 7) / 8;
   if (g > 256) g = 256;
   const size_t lds = (size_t)(3 * THC_IMG + 2 * 64) * sizeof(frag8) + (3 * 256 + 16) * sizeof(float) + 16;      // (+ the tile counter)
@@ -888,6 +914,11 @@ int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* co
     FRL_LAUNCH_AS("tcn_chain_fwd_kernel<false>", tcn_chain_fwd_kernel<false>, dim3((unsigned)g), dim3(512), lds, stream, (const bf16*)x, a, npix, HW, Ch, eps, g_thc_static ? 0 : 1);
   }
   return frl_check_launch("tcn_chain_fwd");
+}
+int frl_tcn_chain_fwd(const void* x, const float* const* conv_w, const float* const* conv_b, const float* const* gn_w, const float* const* gn_b,
+                      const float* const* gate_w, const float* const* gate_b, const float* head_w, const float* head_b, void* y1, void* y2, void* y3,
+                      void* h, int64_t npix, int HW, int Ch, float eps, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return frl_tcn_chain_fwd_xt(x, conv_w, conv_b, gn_w, gn_b, gate_w, gate_b, head_w, head_b, y1, y2, y3, h, nullptr, npix, HW, Ch, eps, ws, ws_bytes, stream);
 }
 
 // one launch: dx [B][5][HW][64] bf16 and all parameter gradients (float32, reference layouts); drop_mask as in the forward

@@ -147,6 +147,7 @@ SIGNATURES = {
     "frl_tcn_hot_bwd_nodx_supported": (c_int, [L, I]),
     "frl_tcn_chain_fwd_workspace_bytes": (S, []),
     "frl_tcn_chain_fwd": (c_int, [P] * 13 + [L, I, I, F, P, S, P]),
+    "frl_tcn_chain_fwd_xt": (c_int, [P] * 14 + [L, I, I, F, P, S, P]),
     "frl_tcn_block_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, F, I, P, S, P]),
     "frl_decode_codes": (c_int, [P, P, P, L, I, I, I, P, P]),
     "frl_vicreg_workspace_bytes": (S, [L, I]),

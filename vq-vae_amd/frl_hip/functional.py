@@ -335,20 +335,29 @@ class TcnBlockFn(Function):
 class TcnChainHeadFn(Function):
     """Three hot GatedResidualBlocks (dilation 1, 2, 4) + the 1x1 phase head: ONE forward launch (ops.tcn_chain_fwd); the backward runs the
     head's two kernels and the three fused block backward kernels on the saved block inputs x, y1, y2 (and y3 for the head's weights).
-    args: x, 3 x (conv_w, conv_b, gn_w, gn_b, gate_w, gate_b), head_w, head_b, groups, eps."""
+    args: x, 3 x (conv_w, conv_b, gn_w, gn_b, gate_w, gate_b), head_w, head_b, groups, eps[, want_xtype].
+    want_xtype=True: the result is (h, x_type), x_type = the time mean of x as a non-differentiable side output of the same launch."""
 
     @staticmethod
     def forward(ctx, x, *args):
-        params, (head_w, head_b, groups, eps) = args[:18], args[18:]
+        params, (head_w, head_b, groups, eps) = args[:18], args[18:22]
+        want_xtype = len(args) > 22 and bool(args[22])
         blocks = [tuple(params[6 * i:6 * i + 6]) + (d, groups, False) for i, d in enumerate((1, 2, 4))]
-        y1, y2, y3, h = ops.tcn_chain_fwd(x, blocks, head_w, head_b, eps)
+        y1, y2, y3, h, *xt = ops.tcn_chain_fwd(x, blocks, head_w, head_b, eps, want_xtype=want_xtype)
         ctx.cfg = (groups, eps)
+        ctx.n_tail = len(args) - 20
         ctx.save_for_backward(x, y1, y2, y3, head_w, *params)
+        if want_xtype:
+            ctx.mark_non_differentiable(xt[0])
+            ctx.set_materialize_grads(False)                        # (no zero-filled "gradient" of x_type: 33 MB per step at cfg2)
+            return h, xt[0]
         return h
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, dh):
+    def backward(ctx, dh, _dxt=None):
+        if dh is None:
+            return (None,) * (21 + ctx.n_tail)
         x, y1, y2, y3, head_w, *params = ctx.saved_tensors
         groups, eps = ctx.cfg
         dh = _c(dh)
@@ -369,7 +378,7 @@ class TcnChainHeadFn(Function):
                 g = ops.tcn_block_bwd(xin, dy, cw, cb, gw, gb, tw, tb, None, None, dil, groups, eps, want_dx=(i > 0 or ctx.needs_input_grad[0]))
             grads[6 * i:6 * i + 6] = [g["conv_w"], g["conv_b"], g["gn_w"], g["gn_b"], g["gate_w"], g["gate_b"]]
             dy = g["dx"]
-        return (dy if ctx.needs_input_grad[0] else None,) + _wanted(ctx, 1, grads) + (dw_h, db_h, None, None)
+        return (dy if ctx.needs_input_grad[0] else None,) + _wanted(ctx, 1, grads) + (dw_h, db_h) + (None,) * ctx.n_tail
 
 
 class FilmFn(Function):

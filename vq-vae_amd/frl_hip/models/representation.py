@@ -155,11 +155,29 @@ class RepresentationModel(nn.Module):
                 return Fh.TcnChainHeadFn.apply(x, *flat, head.weight, head.bias, layers[0].norm.num_groups, layers[0].norm.eps)
         return head(tcn(x))
 
-    def forward_phase_nhwc(self, x_phase: torch.Tensor, z_type: torch.Tensor, return_parts: bool = False, inference: bool = False):
+    def phase_chain_xtype(self, x: torch.Tensor):
+        """Training path of the hot configuration: phase_tcn -> phase_head on x [B,T,HW..,C] with the type path's input as a side output
+        of the same launch: -> (h, x_type), x_type [B,HW..,C] = the time mean of x (no gradient), bit for bit ops.mean_time(x).
+        None when the one-launch chain does not serve this configuration (the caller then uses ops.mean_time and forward_phase_nhwc)."""
+        tcn, head = self.phase_tcn, self.phase_head
+        layers = list(tcn.layers)
+        if len(layers) != 3 or head.k != 1 or head.bias is None or any(self.training and l.dropout.p > 0.0 for l in layers):
+            return None
+        blocks = [(l.conv.weight, l.conv.bias, l.norm.weight, l.norm.bias, l.gate.weight, l.gate.bias, l.dilation, l.norm.num_groups,
+                   l.needs_projection) for l in layers]
+        if not ops.tcn_chain_supported(x, blocks, head.weight):
+            return None
+        flat = [t for blk in blocks for t in blk[:6]]
+        return Fh.TcnChainHeadFn.apply(x, *flat, head.weight, head.bias, layers[0].norm.num_groups, layers[0].norm.eps, True)
+
+    def forward_phase_nhwc(self, x_phase: torch.Tensor, z_type: torch.Tensor, return_parts: bool = False, inference: bool = False,
+                           h: Optional[torch.Tensor] = None):
         """x_phase [B,T,H,W,C_phase], z_type [B,H,W,d] (caller stop-grads) -> z_phase [B,T,H,W,zp].
-        inference=True: forward only (the caller runs under no_grad), the phase chain skips what only its backward reads."""
+        inference=True: forward only (the caller runs under no_grad), the phase chain skips what only its backward reads.
+        h: the phase head's output when the caller has already run the chain on x_phase (phase_chain_xtype)."""
         self._require_gpu(x_phase)
-        h = self._phase_chain(self._rows(x_phase), inference=inference)
+        if h is None:
+            h = self._phase_chain(self._rows(x_phase), inference=inference)
         zt = self._rows(z_type)
         film = self.phase_film
         gn, bn = film.gamma_network, film.beta_network

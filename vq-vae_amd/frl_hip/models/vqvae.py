@@ -172,6 +172,10 @@ class VQVAE(RepresentationModel):
         # promise that out["loss"] is differentiated with upstream 1.  False: the forward / backward kernel pair (A/B runs, and callers
         # that scale out["loss"] before .backward() -- a broken promise is reported by ops.check_grad_scale()).
         self.onepass_decoder = True
+        # forward_tiles takes x_type (the time mean of the tile) from the phase encoder's forward launch, which holds the tile's rows in
+        # registers anyway, where that one-launch chain applies (RepresentationModel.phase_chain_xtype); the result is bit for bit
+        # ops.mean_time(tile).  False: the separate mean_time pass (A/B runs).
+        self.chain_xtype = True
         self._grad_scale_dev = {}
         # The phase path is conditioned on stopgrad(z_type): forward AND backward of the two branches are independent, so the phase
         # branch runs on a side HIP stream next to VQ + type decoder (forward) and next to the whole type-path backward.
@@ -219,11 +223,12 @@ class VQVAE(RepresentationModel):
         xhat = dec(z)
         return Fh.mse_loss(xhat, target, mask), xhat
 
-    def _phase_branch(self, tile, z_type_detached, mask, return_recon, onepass: bool = False) -> Dict[str, torch.Tensor]:
-        """Dense phase path -> (optional phase codebook) -> phase decoder + masked L2; returns its outputs and `loss_terms`."""
+    def _phase_branch(self, tile, z_type_detached, mask, return_recon, onepass: bool = False, h=None) -> Dict[str, torch.Tensor]:
+        """Dense phase path -> (optional phase codebook) -> phase decoder + masked L2; returns its outputs and `loss_terms`.
+        h: the phase head's output when forward_tiles has already run the chain (together with x_type)."""
         b, t, hh, ww, f = tile.shape
         out: Dict[str, torch.Tensor] = {}
-        z_phase = self.forward_phase_nhwc(tile, z_type_detached)            # [B,T,H,W,zp]
+        z_phase = self.forward_phase_nhwc(tile, z_type_detached, h=h)       # [B,T,H,W,zp]
         zp_in = z_phase
         terms = []                                                          # (loss term, weight) pairs, summed by forward_tiles in one launch
         if hasattr(self, "quant_phase"):
@@ -256,14 +261,34 @@ class VQVAE(RepresentationModel):
         self._require_gpu(tile)
         tile = self._rows(tile)
         b, t, hh, ww, f = tile.shape
-        with torch.no_grad():
-            x_type = ops.mean_time(tile)                                   # [B,H,W,F]
+        concurrent = self.phase and self.concurrent_phase and tile.is_cuda
+        pre = None
+        if self.phase and self.chain_xtype and tile.is_cuda and not differentiable_vq_loss:
+            # the phase encoder runs first and hands x_type over as a side output.  It stays on the phase stream (autograd replays its
+            # backward there, next to the type-path backward); the type path waits for it, the rest of the phase branch for z_type below
+            if concurrent:
+                main, side = torch.cuda.current_stream(), self.phase_stream(tile.device)
+                side.wait_stream(main)
+                tile.record_stream(side)
+                with torch.cuda.stream(side):
+                    pre = self.phase_chain_xtype(tile)
+                if pre is not None:
+                    main.wait_stream(side)
+                    pre[1].record_stream(main)
+            else:
+                pre = self.phase_chain_xtype(tile)
+        if pre is not None:
+            h_phase, x_type = pre                                          # [B,T,H,W,zp], [B,H,W,F]
+        else:
+            h_phase = None
+            with torch.no_grad():
+                x_type = ops.mean_time(tile)                               # [B,H,W,F]
         z_type, gate = self.forward_nhwc(x_type, return_gate=True)          # [B,H,W,d]
         side = ph = None
         # the decoder losses join the total below with the weight lambda_recon and out["loss"] is differentiated as it is (the legacy
         # contract's caller builds its own total: no promise there)
         onepass = self.training and not differentiable_vq_loss
-        if self.phase and self.concurrent_phase and tile.is_cuda:
+        if concurrent:
             main, side = torch.cuda.current_stream(), self.phase_stream(tile.device)
             side.wait_stream(main)
             zt = z_type.detach()
@@ -272,7 +297,7 @@ class VQVAE(RepresentationModel):
             if mask is not None:
                 mask.record_stream(side)
             with torch.cuda.stream(side):
-                ph = self._phase_branch(tile, zt, mask, return_recon, onepass)
+                ph = self._phase_branch(tile, zt, mask, return_recon, onepass, h_phase)
         d = z_type.shape[-1]
         # gradient quantizer on the GPU: its two loss parts join the total below directly (one launch yields the total, the flag and vq_loss)
         split_vq = self.quant.quantizer != "ema" and z_type.is_cuda and not differentiable_vq_loss
@@ -303,7 +328,7 @@ class VQVAE(RepresentationModel):
                     if torch.is_tensor(v):
                         v.record_stream(main)
             else:
-                ph = self._phase_branch(tile, z_type.detach(), mask, return_recon, onepass)
+                ph = self._phase_branch(tile, z_type.detach(), mask, return_recon, onepass, h_phase)
             terms += ph.pop("loss_terms")
             out.update(ph)
         # weighted sum of the loss terms and its isfinite flag in ONE launch (the trainer's device-side guard reads out["loss_ok"])

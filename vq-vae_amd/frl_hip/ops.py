@@ -1049,9 +1049,11 @@ def tcn_chain_supported(x: torch.Tensor, blocks, head_w: torch.Tensor) -> bool:
 
 
 @_timed("tcn_chain_fwd")
-def tcn_chain_fwd(x, blocks, head_w, head_b, eps: float = 1e-5, keep_intermediates: bool = True):
+def tcn_chain_fwd(x, blocks, head_w, head_b, eps: float = 1e-5, keep_intermediates: bool = True, want_xtype: bool = False):
     """x [B,5,HW..,64] -> (y1, y2, y3 [same shape], h [B,5,HW..,Ch]).  keep_intermediates=False runs the inference variant of the
-    launch: y1, y2, y3 (kept for the backward only) are neither allocated nor written and come back as None; h is the same, bit for bit."""
+    launch: y1, y2, y3 (kept for the backward only) are neither allocated nor written and come back as None; h is the same, bit for bit.
+    want_xtype=True: the launch also writes the time mean of x ([B,HW..,64], bit for bit mean_time(x): the rows are in its registers
+    anyway) and the result is (y1, y2, y3, h, x_type); a tensor instead of True is the buffer to write x_type into (>= B*HW*64 elements)."""
     b, t, c = x.shape[0], x.shape[1], x.shape[-1]
     hw = x.numel() // (b * t * c)
     _chk_rows(x, c, "tcn_chain_fwd.x")
@@ -1060,12 +1062,18 @@ def tcn_chain_fwd(x, blocks, head_w, head_b, eps: float = 1e-5, keep_intermediat
     ws = workspace(lib.frl_tcn_chain_fwd_workspace_bytes(), x.device)
     ys = [torch.empty_like(x) for _ in range(3)] if keep_intermediates else [None] * 3
     h = torch.empty(x.shape[:-1] + (ch,), dtype=x.dtype, device=x.device)
+    if torch.is_tensor(want_xtype):
+        xt, want_xtype = want_xtype, True
+        if xt.dtype != x.dtype or xt.device != x.device or not xt.is_contiguous() or xt.numel() < b * hw * c:
+            raise ValueError("tcn_chain_fwd: the x_type buffer must be contiguous, of x's dtype and device, with >= B*HW*C elements")
+    else:
+        xt = torch.empty((b,) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device) if want_xtype else None
     arr = ctypes.c_void_p * 3
     cols = [arr(*[_f32(blk[i] if i != 4 else blk[i].reshape(c, c), "tcn parameter").data_ptr() for blk in blocks]) for i in range(6)]
-    check(lib.frl_tcn_chain_fwd(_p(x), *[ctypes.cast(a, ctypes.c_void_p) for a in cols], _p(_f32(head_w.reshape(ch, c), "head_w")), _p(_f32(head_b, "head_b")),
-                                _p(ys[0]), _p(ys[1]), _p(ys[2]), _p(h), b * hw, hw, ch, float(eps), _p(ws), ws.numel(), _stream()),
-          "frl_tcn_chain_fwd")
-    return ys[0], ys[1], ys[2], h
+    check(lib.frl_tcn_chain_fwd_xt(_p(x), *[ctypes.cast(a, ctypes.c_void_p) for a in cols], _p(_f32(head_w.reshape(ch, c), "head_w")),
+                                   _p(_f32(head_b, "head_b")), _p(ys[0]), _p(ys[1]), _p(ys[2]), _p(h), _p(xt), b * hw, hw, ch, float(eps),
+                                   _p(ws), ws.numel(), _stream()), "frl_tcn_chain_fwd_xt")
+    return (ys[0], ys[1], ys[2], h, xt) if want_xtype else (ys[0], ys[1], ys[2], h)
 
 
 @_timed("tcn_block_bwd")
