@@ -501,6 +501,28 @@ int frl_soft_nbr_gathered_bwd(const float* ref, int C, const void* emb, int D, i
                               int exclude_diagonal, float inv_tau_ref, float inv_tau_learned, int min_valid, const float* pairstat,
                               const float* out2, const float* gup, float* grad_rows, frl_stream_t stream);
 
+/* ---- EVT soft-neighbourhood loss (csrc/evt_soft_neighborhood.hip) -------------------------------------------------------------
+ * evt_soft_neighborhood_loss of frl/losses/evt_soft_neighborhood.py:266-440 for every segment (one sample's anchors) of emb [N][D]
+ * (dtype 0 = float32, 1 = bfloat16, D <= 256) at once, all pairs of a segment, no [M][M] array in memory.  idx [N] int32 = the anchors'
+ * code indices, -1 = unknown code (an idx >= K is treated as unknown and sets *index_flag to 1; the pointer may be NULL); S [K][K] f32 the
+ * diffused similarity (not symmetric), w [K] f32 the code weights; seg [nseg + 1] int32 row offsets on the device and the same offsets
+ * on the host, validated there (0 = seg[0] <= .. <= seg[nseg] = N, any length including 0; nseg <= 65535).  Anchor i is valid iff
+ * idx[i] >= 0; pair (i, j) is in the mask iff both are valid and idx[i] != idx[j]; a row is active with >= 2 pairs; a_ij =
+ * -(1 - S[idx_i][idx_j]) * inv_tau_ref, b_ij = -|e_i - e_j|_2 * inv_tau_learned, KL_i = KL(softmax_j a || softmax_j b) over the mask,
+ * loss_s = sum w[idx_i] KL_i / W_s over the active rows (W_s = their weights); 0 with fewer than min_valid_anchors valid anchors or W_s <= 0.
+ * rowstat [N][10] f32 = KL, log sum e^a, max b, log sum e^(b - max), H(p), H(q), pairs in the mask, confused pairs (1 - S < 1 - 1e-6),
+ * sum of d over confused pairs, over the others.  segout [nseg][2] f32 = loss_s, W_s (0 when the segment contributes nothing).
+ * segstat [nseg][12] f64 = loss_s, live, valid anchors, active rows, sum H(p), sum H(q), confused pairs of active rows, confused pairs,
+ * sum d confused, sum d others, other pairs, W_s.  frl_evt_soft_nbr_bwd recomputes the distances and writes grad [N][D] in emb's dtype,
+ * = gup[s] * seg_weights[s] (NULL = 1) * d loss_s / d emb, every row once (zero where a distance is zero: torch.cdist's convention).
+ * Fixed reduction order, no float atomics: loss and gradients are bit-reproducible. */
+int frl_evt_soft_nbr_fwd(const void* emb, int emb_dtype, int64_t N, int D, const int32_t* idx, const float* S, const float* w, int K,
+                         const int32_t* seg, const int32_t* seg_host, int nseg, float inv_tau_ref, float inv_tau_learned, int min_valid_anchors,
+                         float* rowstat, float* segout, double* segstat, int32_t* index_flag, frl_stream_t stream);
+int frl_evt_soft_nbr_bwd(const void* emb, int emb_dtype, int64_t N, int D, const int32_t* idx, const float* S, const float* w, int K,
+                         const int32_t* seg, const int32_t* seg_host, int nseg, float inv_tau_ref, float inv_tau_learned, const float* rowstat,
+                         const float* segout, const float* gup, const float* seg_weights, void* grad, frl_stream_t stream);
+
 /* ---- code-map decoding (csrc/codes.hip) --------------------------------------------------------------------------------------
  * frl_decode_codes: out[p][:] = table[idx[p]][:] for a decoded-code table [K][F] (dtype 0 = float32, 1 = bfloat16; the VQ-VAE decoder
  * applied to the K codebook rows), idx [P] int32.  Indices in [-K, 0) wrap to idx + K; any other out-of-range index is clamped into

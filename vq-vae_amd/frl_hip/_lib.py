@@ -157,6 +157,8 @@ SIGNATURES = {
     "frl_soft_nbr_bwd": (c_int, [P, P, P, P, P, L, I, P, P]),
     "frl_soft_nbr_gathered_fwd": (c_int, [P, I, P, I, I, P, P, P, P, P, P, L, I, I, F, F, I, P, P, P, P]),
     "frl_soft_nbr_gathered_bwd": (c_int, [P, I, P, I, I, P, P, P, P, P, P, L, I, I, F, F, I, P, P, P, P, P]),
+    "frl_evt_soft_nbr_fwd": (c_int, [P, I, L, I, P, P, P, I, P, P, I, F, F, I, P, P, P, P, P]),
+    "frl_evt_soft_nbr_bwd": (c_int, [P, I, L, I, P, P, P, I, P, P, I, F, F, P, P, P, P, P, P]),
 }
 
 

@@ -3,3 +3,4 @@ from .contrastive import contrastive_loss  # noqa: F401
 from .variance_covariance import variance_covariance_loss, variance_loss, covariance_loss  # noqa: F401
 from .soft_neighborhood import (soft_neighborhood_matching_loss, soft_neighborhood_loss_gathered, phase_alignment,  # noqa: F401
                                 phase_neighborhood_loss)
+from .evt_soft_neighborhood import EvtDiffusionMetric, evt_soft_neighborhood_loss, evt_soft_neighborhood_loss_batched  # noqa: F401

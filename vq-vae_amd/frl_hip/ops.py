@@ -1521,3 +1521,80 @@ def soft_nbr_gathered_bwd(ref: torch.Tensor, emb: torch.Tensor, rows: torch.Tens
                                                 1.0 / float(tau_learned), int(min_valid_per_row), _p(pairstat), _p(out2), _p(g), _p(grows),
                                                 _stream()), "frl_soft_nbr_gathered_bwd")
     return grows
+
+
+# ----------------------------------------------------------------------------------------------
+# EVT soft-neighbourhood loss (csrc/evt_soft_neighborhood.hip)
+# ----------------------------------------------------------------------------------------------
+EVT_SOFT_NBR_MAX_WIDTH = 256
+
+
+def _chk_evt_soft_nbr(name: str, emb, idx, table, code_weights, seg, seg_host, tau_ref: float, tau_learned: float):
+    """Shape limits first (they hold on any device), then the device, then the layouts -> (N, D, K, segments)."""
+    if emb.dim() != 2 or idx.dim() != 1 or idx.shape[0] != emb.shape[0]:
+        raise ValueError(f"{name}: expected emb [N, D] and idx [N], got {tuple(emb.shape)} and {tuple(idx.shape)}")
+    n, d = emb.shape
+    if d > EVT_SOFT_NBR_MAX_WIDTH:
+        raise ValueError(f"{name}: supports D <= {EVT_SOFT_NBR_MAX_WIDTH}, got D = {d}")
+    if not (tau_ref > 0 and tau_learned > 0):
+        raise ValueError(f"{name}: temperatures must be positive, got tau_ref={tau_ref} tau_learned={tau_learned}")
+    if not (emb.is_cuda and idx.is_cuda and table.is_cuda and code_weights.is_cuda and seg.is_cuda):
+        raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+    if n < 1 or d < 1:
+        raise ValueError(f"{name}: needs at least one row and one column")
+    if emb.dtype not in (torch.float32, torch.bfloat16) or not emb.is_contiguous():
+        raise ValueError(f"{name}: emb must be contiguous float32 or bfloat16 rows")
+    if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != emb.device:
+        raise ValueError(f"{name}: idx must be a contiguous int32 [{n}] tensor on the device of emb")
+    k = table.shape[0] if table.dim() == 2 else 0
+    if table.dim() != 2 or table.shape[1] != k or k < 1 or table.dtype != torch.float32 or not table.is_contiguous() or table.device != emb.device:
+        raise ValueError(f"{name}: the similarity table must be a contiguous float32 [K, K] tensor on the device of emb")
+    if code_weights.dtype != torch.float32 or code_weights.shape != (k,) or not code_weights.is_contiguous() or code_weights.device != emb.device:
+        raise ValueError(f"{name}: the code weights must be a contiguous float32 [{k}] tensor on the device of emb")
+    if seg_host.is_cuda or seg_host.dtype != torch.int32 or seg_host.dim() != 1 or seg_host.numel() < 2 or not seg_host.is_contiguous():
+        raise ValueError(f"{name}: the host segment offsets must be a contiguous int32 [segments + 1] CPU tensor")
+    if seg.dtype != torch.int32 or seg.shape != seg_host.shape or not seg.is_contiguous() or seg.device != emb.device:
+        raise ValueError(f"{name}: the device segment offsets must be a contiguous int32 [{seg_host.numel()}] tensor on the device of emb")
+    return n, d, k, seg_host.numel() - 1
+
+
+@_timed("evt_soft_nbr_fwd")
+def evt_soft_nbr_fwd(emb: torch.Tensor, idx: torch.Tensor, table: torch.Tensor, code_weights: torch.Tensor, seg: torch.Tensor,
+                     seg_host: torch.Tensor, tau_ref: float = 0.5, tau_learned: float = 0.5, min_valid_anchors: int = 4):
+    """emb [N, D] float32 | bfloat16, idx [N] int32 code indices (-1 = unknown; >= K is treated as unknown and flagged for
+    `index_errors()`), table [K, K] float32, code_weights [K] float32, seg int32 [S + 1] row offsets on the device and seg_host the same
+    on the host (validated there) -> (segout f32 [S, 2] = per-segment loss, active weight; segstat f64 [S, 12]; rowstat f32 [N, 10]):
+    include/frl_hip.h names the columns.  With FRL_HIP_CHECK_INDICES=1 an idx >= K raises IndexError on the spot (one sync per call)."""
+    import os
+    n, d, k, s = _chk_evt_soft_nbr("evt_soft_nbr_fwd", emb, idx, table, code_weights, seg, seg_host, tau_ref, tau_learned)
+    dev = emb.device
+    rowstat = torch.empty(n, 10, dtype=torch.float32, device=dev)
+    segout = torch.empty(s, 2, dtype=torch.float32, device=dev)
+    segstat = torch.empty(s, 12, dtype=torch.float64, device=dev)
+    check_now = os.environ.get("FRL_HIP_CHECK_INDICES", "0") == "1"
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if check_now else _index_flag(dev)
+    check(_lib.load().frl_evt_soft_nbr_fwd(_p(emb), _dt(emb), n, d, _p(idx), _p(table), _p(code_weights), k, _p(seg), _p(seg_host), s,
+                                           1.0 / float(tau_ref), 1.0 / float(tau_learned), int(min_valid_anchors), _p(rowstat), _p(segout),
+                                           _p(segstat), _p(flag), _stream()), "frl_evt_soft_nbr_fwd")
+    if check_now:
+        _index_flag(dev).bitwise_or_(flag)
+        if bool(flag.item()):
+            raise IndexError(f"evt_soft_nbr_fwd: code index out of range for {k} codes")
+    return segout, segstat, rowstat
+
+
+@_timed("evt_soft_nbr_bwd")
+def evt_soft_nbr_bwd(emb: torch.Tensor, idx: torch.Tensor, table: torch.Tensor, code_weights: torch.Tensor, seg: torch.Tensor,
+                     seg_host: torch.Tensor, tau_ref: float, tau_learned: float, rowstat: torch.Tensor, segout: torch.Tensor, gup: torch.Tensor,
+                     seg_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d emb [N, D] in emb's dtype for the outputs of evt_soft_nbr_fwd: the sum over segments of gup[s] * seg_weights[s] * d loss_s / d emb
+    (gup, seg_weights: float32 [S] on the device; seg_weights None = ones).  Every row is written once."""
+    n, d, k, s = _chk_evt_soft_nbr("evt_soft_nbr_bwd", emb, idx, table, code_weights, seg, seg_host, tau_ref, tau_learned)
+    for t, shape, name in ((rowstat, (n, 10), "rowstat"), (segout, (s, 2), "segout"), (gup, (s,), "gup"), (seg_weights, (s,), "seg_weights")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != emb.device):
+            raise ValueError(f"evt_soft_nbr_bwd: {name} must be a contiguous float32 {shape} tensor on the device of emb")
+    grad = torch.empty_like(emb)
+    check(_lib.load().frl_evt_soft_nbr_bwd(_p(emb), _dt(emb), n, d, _p(idx), _p(table), _p(code_weights), k, _p(seg), _p(seg_host), s,
+                                           1.0 / float(tau_ref), 1.0 / float(tau_learned), _p(rowstat), _p(segout), _p(gup), _p(seg_weights),
+                                           _p(grad), _stream()), "frl_evt_soft_nbr_bwd")
+    return grad
