@@ -316,19 +316,22 @@ int frl_tcn_hot_bwd4_share(int variant, int share);
 
 /* ---- optimizer step (frl/training/representation/step.py:1081-1087: clip_grad_norm_(1.0) then AdamW.step()) ---------------
  * Two launches for the whole parameter set.  desc: HOST table of ntensors records {float* p; const float* g; float* m; float* v;
- * int64_t n; float weight_decay; int lag} (48 bytes; lag = updates the tensor skipped) -- it travels in the kernel-argument
+ * int64_t n; float weight_decay; int slot} (48 bytes; slot = the tensor's entry in tensor_steps) -- it travels in the kernel-argument
  * segment, so moved gradient buffers cost no copy or sync; chunks: DEVICE table of nchunks int32 pairs {tensor index,
  * 4096-element window} sorted by tensor, chunk_tensor: its tensor column on the HOST.  step is the 1-based update count (bias
  * corrections in float64 as torch.optim.AdamW); max_norm <= 0 disables clipping; norm_out (device float, may be NULL) receives
  * the pre-clip global gradient norm.  ok (device float, may be NULL): the reference's isfinite guard evaluated ON THE DEVICE --
  * ok[0] <= 0 leaves parameters and moments untouched; counters (device int[2], may be NULL) = {updates applied, updates skipped},
  * and when given, counters[0] + 1 replaces `step` as the update number (exact under skipped batches, no host sync).
+ * tensor_steps (device int [nsteps], may be NULL): per-tensor update counts as torch.optim.AdamW's state["step"].  The step bumps
+ * entry `slot` of every record when -- and only when -- the device applies the update, and the bias corrections of that tensor use the
+ * entry; slots must be distinct and in [0, nsteps).  A tensor outside the table, a skipped batch and a graph replay leave it exact.
  * lr_dev (device float, may be NULL): when given, lr_dev[0] replaces `lr` -- the learning rate of a train step captured in a
  * hipGraph is written to that word before every replay (per-batch scheduler.step() of loops.py:110 without re-capturing). */
 size_t frl_adamw_workspace_bytes(void);
 int frl_adamw_clip_step(const void* desc_host, int ntensors, const void* chunks, const int* chunk_tensor, int nchunks, float max_norm,
                         float lr, double beta1, double beta2, float eps, int step, float* norm_out, const float* ok, int* counters,
-                        const float* lr_dev, void* ws, size_t ws_bytes, frl_stream_t stream);
+                        const float* lr_dev, int* tensor_steps, int nsteps, void* ws, size_t ws_bytes, frl_stream_t stream);
 /* dst[i] = scale * src[i] over a HOST table of {const float* src; float* dst; int64_t n} records (24 bytes; src NULL -> zeros):
  * flattens the scattered gradients of a bucket for the data-parallel all-reduce in one launch. */
 int frl_multi_tensor_scale_copy(const void* desc_host, int ntensors, const void* chunks, const int* chunk_tensor, int nchunks, float scale,

@@ -18,7 +18,7 @@ struct FrlParamDesc {      // one per tensor, device-resident table
   float* v;
   int64_t n;
   float weight_decay;
-  int lag;                 // updates this tensor has skipped (no gradient): torch.optim.AdamW counts steps per parameter
+  int slot;                // this tensor's entry in tensor_steps (its update count): torch.optim.AdamW counts steps per parameter
 };
 
 #define OPT_CHUNK 4096
@@ -31,18 +31,20 @@ struct FrlParamBatch { FrlParamDesc d[OPT_BATCH]; };
 // count stay untouched and counters[1] is incremented.
 // (count_ok / counters: the FIRST squared-norm launch of a step also bumps the update counters -- applied or skipped -- so that the AdamW
 // launches behind it read the new count and no separate one-thread launch is needed)
+// tensor_steps [.] (device, optional): per-tensor update counts.  The workgroup that owns a tensor's window-0 chunk bumps the tensor's
+// entry when the update is applied, so an entry counts exactly the updates the DEVICE applied to that tensor -- a tensor outside the
+// table (no gradient), a skipped batch and a graph replay (no host code runs) all leave it right.
 __global__ __launch_bounds__(256) void frl_grad_sqnorm_kernel(const FrlParamBatch tab, int tbase, const int2* __restrict__ chunks,
                                                               int nchunks, double* __restrict__ partial, const float* __restrict__ count_ok,
-                                                              int* __restrict__ counters) {
+                                                              int* __restrict__ counters, int* __restrict__ tensor_steps) {
   __shared__ double red[4];
-  if (counters != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    const bool go = (count_ok == nullptr) || (count_ok[0] > 0.f);
-    counters[go ? 0 : 1] += 1;
-  }
+  const bool go = (count_ok == nullptr) || (count_ok[0] > 0.f);
+  if (counters != nullptr && blockIdx.x == 0 && threadIdx.x == 0) counters[go ? 0 : 1] += 1;
   double s = 0.0;
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int2 ck = chunks[c];
     const FrlParamDesc& d = tab.d[ck.x - tbase];
+    if (tensor_steps != nullptr && go && ck.y == 0 && threadIdx.x == 0) tensor_steps[d.slot] += 1;
     const int64_t lo = (int64_t)ck.y * OPT_CHUNK;
     const int64_t hi = lo + OPT_CHUNK < d.n ? lo + OPT_CHUNK : d.n;
     float a = 0.f;
@@ -59,11 +61,12 @@ __global__ __launch_bounds__(256) void frl_adamw_kernel(const FrlParamBatch tab,
                                                         const double* __restrict__ partial, int npartial, float max_norm, float lr,
                                                         double beta1d, double beta2d, float eps, int step_host,
                                                         float* __restrict__ norm_out, const float* __restrict__ ok, int* counters,
-                                                        int last_batch, const float* __restrict__ lr_dev) {
+                                                        int last_batch, const float* __restrict__ lr_dev,
+                                                        const int* __restrict__ tensor_steps) {
   __shared__ float coef_s;
   if (lr_dev != nullptr) lr = lr_dev[0];                     // learning rate kept on the device (a captured graph replays with new values)
   const bool go = (ok == nullptr) || (ok[0] > 0.f);
-  // update number: device counter + 1 when the caller keeps one (exact under skipped batches), else the host's count
+  // update number without tensor_steps: the device counter when the caller keeps one, else the host's count -- the same for every tensor
   const int step = (counters != nullptr) ? counters[0] : step_host;   // (already bumped by the step's first frl_grad_sqnorm_kernel launch)
   (void)last_batch;
   if (!go) return;
@@ -86,8 +89,9 @@ __global__ __launch_bounds__(256) void frl_adamw_kernel(const FrlParamBatch tab,
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int2 ck = chunks[c];
     const FrlParamDesc& d = tab.d[ck.x - tbase];
-    // bias corrections in float64 from this tensor's own update count, as the Python scalars of torch.optim.AdamW
-    const double tstep = (double)(step - d.lag);
+    // bias corrections in float64 from this tensor's own update count (bumped by this step's squared-norm launch), as the Python
+    // scalars of torch.optim.AdamW
+    const double tstep = (double)(tensor_steps != nullptr ? tensor_steps[d.slot] : step);
     const float step_size = lr / (float)(1.0 - pow(beta1d, tstep));
     const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2d, tstep));
     const int64_t lo = (int64_t)ck.y * OPT_CHUNK;
@@ -160,15 +164,19 @@ size_t frl_adamw_workspace_bytes(void) { return 4096 * sizeof(double); }
 
 // desc [ntensors] is a HOST table of 48-byte records; chunks / chunk_tensor as above; step is the 1-based update count.
 // norm_out (device, optional) receives the pre-clip global gradient norm.  max_norm <= 0 disables clipping.
+// tensor_steps (device int [nsteps], optional): per-tensor update counts, indexed by the records' slot field (distinct per record).
 int frl_adamw_clip_step(const void* desc_host, int ntensors, const void* chunks, const int* chunk_tensor, int nchunks, float max_norm,
                         float lr, double beta1, double beta2, float eps, int step, float* norm_out, const float* ok, int* counters,
-                        const float* lr_dev, void* ws, size_t ws_bytes, hipStream_t stream) {
+                        const float* lr_dev, int* tensor_steps, int nsteps, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (ntensors <= 0 || nchunks <= 0) return frl_fail(-2, "adamw: empty parameter table");
   if (step < 1 && counters == nullptr) return frl_fail(-2, "adamw: step must be >= 1");
   if (ws == nullptr || ws_bytes < frl_adamw_workspace_bytes()) return frl_fail(-4, "adamw: workspace too small");
   const int nbatch = (ntensors + OPT_BATCH - 1) / OPT_BATCH;
   if (nbatch * 512 > 4096) return frl_fail(-2, "adamw: more than 576 parameter tensors per call");
   const FrlParamDesc* dh = (const FrlParamDesc*)desc_host;
+  if (tensor_steps != nullptr)
+    for (int i = 0; i < ntensors; ++i)
+      if (dh[i].slot < 0 || dh[i].slot >= nsteps) return frl_fail(-2, "adamw: a record's slot is outside tensor_steps");
   double* partial = (double*)ws;
   int npartial = 0;
   for (int pass = 0; pass < 2; ++pass) {                      // pass 0: partial sums of g^2 of every batch; pass 1: updates
@@ -182,11 +190,12 @@ int frl_adamw_clip_step(const void* desc_host, int ntensors, const void* chunks,
         const int grid = (c1 - c0) < 512 ? (c1 - c0) : 512;
         if (pass == 0) {
           FRL_LAUNCH(frl_grad_sqnorm_kernel, dim3(grid), dim3(256), 0, stream, tab, t0, (const int2*)chunks + c0, c1 - c0, partial + poff, ok,
-                     poff == 0 ? counters : (int*)nullptr);
+                     poff == 0 ? counters : (int*)nullptr, tensor_steps);
           poff += grid;
         } else {
           FRL_LAUNCH(frl_adamw_kernel, dim3(grid), dim3(256), 0, stream, tab, t0, (const int2*)chunks + c0, c1 - c0, (const double*)partial,
-                     npartial, max_norm, lr, beta1, beta2, eps, step, norm_out, ok, counters, (t0 + OPT_BATCH >= ntensors) ? 1 : 0, lr_dev);
+                     npartial, max_norm, lr, beta1, beta2, eps, step, norm_out, ok, counters, (t0 + OPT_BATCH >= ntensors) ? 1 : 0, lr_dev,
+                     (const int*)tensor_steps);
         }
       }
       c0 = c1;

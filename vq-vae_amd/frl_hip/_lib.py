@@ -122,7 +122,7 @@ SIGNATURES = {
     "frl_tcn_block_bwd_fused_workspace_bytes": (S, [L]),
     "frl_tcn_block_bwd_fused": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, F, P, S, P]),
     "frl_adamw_workspace_bytes": (S, []),
-    "frl_adamw_clip_step": (c_int, [P, I, P, P, I, F, F, D, D, F, I, P, P, P, P, P, S, P]),
+    "frl_adamw_clip_step": (c_int, [P, I, P, P, I, F, F, D, D, F, I, P, P, P, P, P, I, P, S, P]),
     "frl_multi_tensor_scale_copy": (c_int, [P, I, P, P, I, F, P]),
     "frl_tcn_hot_supported": (c_int, [I, I, I, I, I, I, I]),
     "frl_tcn_hot_fwd_workspace_bytes": (S, []),

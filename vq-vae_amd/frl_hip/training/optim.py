@@ -18,6 +18,7 @@ from .. import _lib
 from ..ops import _stream, check, workspace
 
 CHUNK = 4096
+MAX_TENSORS = 576                                          # tensors with a gradient per step (frl_adamw_clip_step: 8 batches of 72 records)
 
 
 def chunk_table(numels: Sequence[int]) -> torch.Tensor:
@@ -52,7 +53,9 @@ class HipAdamW:
         self.device = self.params[0].device
         self.exp_avg = [torch.zeros_like(p) for p in self.params]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
-        self.lag = [0] * len(self.params)                  # updates each tensor skipped (torch counts steps per parameter)
+        # updates the device applied to each tensor (torch counts steps per parameter): bumped by the kernels, so it stays exact under
+        # device-skipped batches, tensors without a gradient and graph replays
+        self.tensor_steps = torch.zeros(len(self.params), dtype=torch.int32, device=self.device)
         self._key = None
         self._desc = None
         self._chunks = None
@@ -71,11 +74,11 @@ class HipAdamW:
 
     def _table(self, grads: List[Optional[torch.Tensor]]):
         """Device tables over the parameters that HAVE a gradient (torch.optim.AdamW skips the others entirely)."""
-        key = tuple(g.data_ptr() if g is not None else 0 for g in grads) + tuple(self.lag)
+        key = tuple(g.data_ptr() if g is not None else 0 for g in grads)
         if key != self._key:                               # gradient buffers moved (or first step): rebuild the HOST record table
             live = [i for i, g in enumerate(grads) if g is not None]
             raw = b"".join(struct.pack("<QQQQqfi", self.params[i].data_ptr(), grads[i].data_ptr(), self.exp_avg[i].data_ptr(),
-                                       self.exp_avg_sq[i].data_ptr(), self.params[i].numel(), self.wd[i], self.lag[i]) for i in live)
+                                       self.exp_avg_sq[i].data_ptr(), self.params[i].numel(), self.wd[i], i) for i in live)
             self._desc = ctypes.create_string_buffer(raw, len(raw)) if live else None
             if tuple(live) != self._live:                  # the chunk table only depends on WHICH tensors take part
                 self._chunks = ChunkTable([self.params[i].numel() for i in live], self.device) if live else None
@@ -91,11 +94,10 @@ class HipAdamW:
         if grads is None:
             grads = [p.grad for p in self.params]
         grads = [g if (g is None or (g.dtype == torch.float32 and g.is_contiguous())) else g.float().contiguous() for g in grads]
+        if sum(g is not None for g in grads) > MAX_TENSORS:
+            raise ValueError(f"HipAdamW: more than {MAX_TENSORS} tensors with a gradient in one step")
         self._keep = grads                                 # keep converted copies alive until the kernels ran
         desc = self._table(grads)
-        for i, g in enumerate(grads):
-            if g is None:
-                self.lag[i] += 1                           # takes effect from the next table build on
         if desc is None:
             self.step_count += 1
             self.grad_norm.zero_()
@@ -111,6 +113,7 @@ class HipAdamW:
                                       float(self.param_groups[0]["eps"]), self.step_count, ctypes.c_void_p(self.grad_norm.data_ptr()),
                                       ctypes.c_void_p(ok.data_ptr()) if ok is not None else None, ctypes.c_void_p(self.counters.data_ptr()),
                                       ctypes.c_void_p(self.lr_dev.data_ptr()) if self.lr_dev is not None else None,
+                                      ctypes.c_void_p(self.tensor_steps.data_ptr()), len(self.params),
                                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()), "frl_adamw_clip_step")
         torch.autograd.graph.increment_version(self.params)     # the kernel wrote through raw pointers: tell torch (version-keyed caches)
         return self.grad_norm
@@ -124,7 +127,8 @@ class HipAdamW:
     # torch-compatible checkpoint payload (frl/training/representation/checkpointing.py stores optimizer.state_dict())
     def state_dict(self) -> dict:
         self.step_count = int(self.counters[0].item()) + 0   # the device counter is authoritative (skipped batches)
-        st = {i: {"step": torch.tensor(float(self.step_count - self.lag[i])), "exp_avg": m, "exp_avg_sq": v}
+        steps = self.tensor_steps.tolist()
+        st = {i: {"step": torch.tensor(float(steps[i])), "exp_avg": m, "exp_avg_sq": v}
               for i, (m, v) in enumerate(zip(self.exp_avg, self.exp_avg_sq))}
         off, groups = 0, []
         for g in self.param_groups:
@@ -139,7 +143,7 @@ class HipAdamW:
         for i, s in sd["state"].items():
             self.exp_avg[int(i)].copy_(s["exp_avg"])
             self.exp_avg_sq[int(i)].copy_(s["exp_avg_sq"])
-            self.lag[int(i)] = self.step_count - steps[int(i)]
+        self.tensor_steps.copy_(torch.tensor([steps.get(i, 0) for i in range(len(self.params))], dtype=torch.int32))
         self.counters[0] = self.step_count
         for g, sg in zip(self.param_groups, sd["param_groups"]):
             for k in ("lr", "weight_decay", "betas", "eps"):

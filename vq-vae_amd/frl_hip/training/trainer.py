@@ -229,7 +229,7 @@ class VQVAETrainer:
     def _snapshot(self):
         m, o = self.model, self.opt
         st = dict(params=[p.detach().clone() for p in o.params], m=[t.clone() for t in o.exp_avg], v=[t.clone() for t in o.exp_avg_sq],
-                  counters=o.counters.clone(), step_count=o.step_count, lag=list(o.lag),
+                  counters=o.counters.clone(), tensor_steps=o.tensor_steps.clone(), step_count=o.step_count,
                   buffers=[b.detach().clone() for b in m.buffers()])
         mgr = getattr(m, "codebook_manager", None)
         if mgr is not None and hasattr(mgr, "window"):
@@ -248,9 +248,10 @@ class VQVAETrainer:
             for a, b in zip(o.exp_avg_sq, st["v"]):
                 a.copy_(b)
             o.counters.copy_(st["counters"])
+            o.tensor_steps.copy_(st["tensor_steps"])
             for b, q in zip(m.buffers(), st["buffers"]):
                 b.copy_(q)
-        o.step_count, o.lag = st["step_count"], list(st["lag"])
+        o.step_count = st["step_count"]
         o._key = None
         self._images_refresh()                                     # the weight images follow the restored parameters
         mgr = getattr(m, "codebook_manager", None)
