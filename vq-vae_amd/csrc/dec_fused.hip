@@ -38,7 +38,7 @@ __device__ __forceinline__ void tile_put(TT* tile, int pitch, int prow, int kc, 
 template <int NFZ>
 __device__ __forceinline__ void dec_chain(float (&h)[32], float (&xh)[16], const LQTile<TT, NFZ>& zt, const frag8* __restrict__ w1,
                                           const frag8* __restrict__ w2, const float* __restrict__ b1q, const float* __restrict__ b2q,
-                                          LQTile<TT, 4>& ht, int lane) {
+                                          LQTile<TT, 4>& ht, int lane, int lane2) {
   f32x4 hacc[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -57,7 +57,7 @@ __device__ __forceinline__ void dec_chain(float (&h)[32], float (&xh)[16], const
   for (int m = 0; m < 4; ++m) {
     xacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < 4; ++s) xacc[m] = mfma16(w2[(m * 4 + s) * 64 + lane], ht.f[s], xacc[m]);
+    for (int s = 0; s < 4; ++s) xacc[m] = mfma16(w2[(m * 4 + s) * 64 + lane2], ht.f[s], xacc[m]);
   }
 #pragma unroll
   for (int j = 0; j < 16; ++j) xh[j] = xacc[j >> 2][j & 3] + b2q[j];
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256, 4) void dec_mse_fwd_kernel(const TT* __restric
     LQTile<TT, 4> ht;
     int lw = lane;
     asm volatile("" : "+v"(lw));                                // (opaque per tile: the weight fragments stay in LDS instead of 96 hoisted registers)
-    dec_chain<NFZ>(h, xh, zt, w1, w2, b1q, b2q, ht, lw);
+    dec_chain<NFZ>(h, xh, zt, w1, w2, b1q, b2q, ht, lw, lw);
     if (valid) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) { const float d = xh[j] - (float)tt.f[j >> 3][j & 7]; sq = fmaf(d, d, sq); }
@@ -175,6 +175,30 @@ __device__ __forceinline__ void df_sg_sync(unsigned* bar, unsigned& gen, int lan
 // release fence and a ticket as in vq_assign_resident_kernel, was measured and dropped: it lengthened the <2,4> kernel by 9 us at 262 k
 // rows and the subgroup kernel by 2..7 us at 1.3 M rows, run-to-run noise included; the finalize launch it would replace costs 5.)
 // n_valid must be known before the pass: la.nv_host (no mask: P * 64) or la.out[1] (dec_mask_count_kernel).
+//
+// CB: 16-wide blocks of the latent in the dz GEMM, the dW1 accumulators and the w1t image: 1 for Cz <= 16, else CZP / 16.  (z -> hidden
+// stays K = 32, the slab keeps its stride CZP: the columns >= 16 of a CB = 1 slab are never written and DecEpi drops every column >= Cz.)
+//
+// PAIR (NFZ = 2, NW = 8: latents of more than 32 channels at two waves per SIMD).  The two 4-wave halves of the workgroup take the rounds
+// of the 4-wave lockstep workgroup <2, 4> two at a time -- half 0 round blockIdx.x + 2 i gridDim.x, half 1 the one after it -- into one
+// 128-row tile set, and all eight waves contract it, each owning half the accumulator tiles of a 4-wave workgroup's wave.  Every
+// accumulator tile therefore meets the same rows in the same order as in <2, 4> on the same grid, and every float32 sum (slabs, loss
+// partials) is bit for bit that kernel's.  The loss chain of a lane of <2, 4> runs over all rounds, so half 1 hands its masked
+// differences to half 0 through the LDS (into the rows of t_h that the receiving wave overwrites next, one more barrier per round pair).
+// Two tile sets fit the LDS only beside THREE weight images, so w2t is not kept (WT):
+// the dxhat -> dhidden fragments come out of the forward image w2 through transposing reads.  Fragment (m, s) of w2t holds, for lane
+// (r, kc) and element e, W2[f = 16 kc + 8 s + e][h = 32 (r >> 2) + 4 m + (r & 3)]; in w2 that element is block mb = 2 s + (e >> 2),
+// k-step m >> 1, lane slot (row 4 kc + (e & 3), quarter r >> 2), element 4 (m & 1) + (r & 3).  ds_read_b64_tr_b16 hands lane r of a
+// 16-lane group element (r & 3) of the 8 bytes that lane 4 e + (r >> 2) of the group points at, so lane j of group kc points at slot
+// (row 4 kc + (j >> 2), quarter j & 3) of block 2 s (e < 4) or 2 s + 1 (e >= 4: 4 KB further), 8 (m & 1) bytes in.  Slots of quarters 2
+// and 3 are stored at row ^ 8 (df_w2_slot): the 32 lanes of a half-wave then meet two to a bank instead of four; ds_read_b128 of the
+// forward fragments stays conflict-free.  The register ring is one round shallower there.
+__device__ __forceinline__ int df_w2_slot(int l) { return l ^ ((l >> 2) & 8); }
+__device__ __forceinline__ bf16x8 df_w2t_frag(const char* a) {
+  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(a));
+  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(a + 4096));
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
 template <bool LOSS> struct DecLoss {};
 template <> struct DecLoss<true> {
   double* partial;      // [gridDim.x][2]
@@ -183,20 +207,24 @@ template <> struct DecLoss<true> {
   float nv_host;        // n_valid when the host knows it, else < 0: read from out[1]
 };
 
-template <int NFZ, int NW, bool SG = false, bool LOSS = false>
+template <int NFZ, int NW, bool SG, bool LOSS, int CB>
 __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const TT* __restrict__ Z, const frag8* __restrict__ Wpk, const float* __restrict__ b1,
                                                                const float* __restrict__ b2, const TT* __restrict__ TGT,
                                                                const uint8_t* __restrict__ mask, const float* __restrict__ gscale,
                                                                const float* __restrict__ stats, TT* __restrict__ DZ, int64_t P, int Cz,
                                                                float* __restrict__ slab, const DecLoss<LOSS> la) {
-  constexpr int CZP = 32 * NFZ, CB = CZP / 16, R = 16 * NW, NTH = SG ? 512 : 64 * NW;
+  constexpr int CZP = 32 * NFZ, R = 16 * NW, NTH = SG ? 512 : 64 * NW;
+  constexpr bool PAIR = !SG && NW == 8 && NFZ == 2, WT = PAIR;
+  constexpr int RR = PAIR ? 64 : R;                           // rows of a round
+  static_assert(!(SG && NFZ == 2), "latents of more than 32 channels: PAIR");
+  static_assert(CB == CZP / 16 || (CB == 1 && NFZ == 1), "latent blocks");
   constexpr int PX = DF_F + 8, PH = DF_H + 8, PZ = CZP + 8;            // LDS tile pitches (16-byte skew)
   static_assert(!SG || NW == 4, "subgroups are four waves");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   frag8* w1 = reinterpret_cast<frag8*>(smem);                 // [8][NFZ][64]     z -> hidden
   frag8* w2 = w1 + 8 * NFZ * 64;                              // [4][4][64]       hidden -> xhat
-  frag8* w2t = w2 + 16 * 64;                                  // [8][2][64]       dxhat -> dhidden
-  frag8* w1t = w2t + 16 * 64;                                 // [CB][4][64]      dhidden -> dz
+  frag8* w2t = w2 + 16 * 64;                                  // [8][2][64]       dxhat -> dhidden (WT: not kept)
+  frag8* w1t = w2t + (WT ? 0 : 16 * 64);                      // [CB][4][64]      dhidden -> dz
   float* tb = reinterpret_cast<float*>(w1t + CB * 4 * 64);    // b1[128] | b2[64]
   const int tid = threadIdx.x, lane = tid & 63;
   const int sg = SG ? (tid >> 8) : 0;                          // subgroup: waves 0-3 / 4-7
@@ -209,7 +237,19 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
   TT* t_z = t_dh + R * PH;                                    // [R][PZ]
   const int px = lane & 15, kc = lane >> 4, r16 = px;
   const int prow = wave * 16 + px;
-  copy_frags_lds<TT>(w1, Wpk, (8 * NFZ + 16 + 16 + CB * 4) * 64, tid, NTH);
+  const int hf = PAIR ? (wave >> 2) : 0;                       // (PAIR) which round of the pair
+  const int rrow = PAIR ? (wave & 3) * 16 + px : prow;         // row inside the round
+  if constexpr (WT) {
+    copy_frags_lds<TT>(w1, Wpk, 8 * NFZ * 64, tid, NTH);
+    for (int i = tid; i < 16 * 64; i += NTH) w2[df_w2_slot(i)] = Wpk[8 * NFZ * 64 + i];
+    copy_frags_lds<TT>(w1t, Wpk + (8 * NFZ + 32) * 64, CB * 4 * 64, tid, NTH);
+  } else {
+    copy_frags_lds<TT>(w1, Wpk, (8 * NFZ + 16 + 16 + CB * 4) * 64, tid, NTH);
+  }
+  const int lane2 = WT ? df_w2_slot(lane) : lane;              // lane slot in the w2 image
+  // (WT) byte address of this lane's 8 bytes of block 0, k-step 0 for the transposing reads
+  const char* w2tr = reinterpret_cast<const char*>(w2) + 16 * df_w2_slot((px & 3) * 16 + 4 * kc + (px >> 2));
+  (void)w2tr;
   for (int i = tid; i < 192; i += NTH) tb[i] = i < 128 ? b1[i] : b2[i - 128];
   if (SG && tid < 2) bars[16 * tid] = 0u;
   unsigned* bar = bars + 16 * sg;
@@ -244,11 +284,11 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
   const bf16 one = (bf16)1.f, zero = (bf16)0.f;
   const bf16x8 ones = (r16 == 0) ? bf16x8{one, one, one, one, one, one, one, one} : bf16x8{zero, zero, zero, zero, zero, zero, zero, zero};
 
-  const int64_t nwt = (P + R - 1) / R;
-  // rounds of this workgroup (SG: of this subgroup): first, step, end
-  int64_t w_first = blockIdx.x, w_end = nwt;
-  const int64_t w_step = gridDim.x;
-  if (SG) {                                                    // the workgroup's rounds blockIdx.x + i gridDim.x, split 19 : 13 between the subgroups
+  const int64_t nwt = (P + RR - 1) / RR;
+  // rounds of this workgroup (SG: of this subgroup; PAIR: of this half, w_end counts for half 0): first, step, end
+  int64_t w_first = blockIdx.x + (PAIR ? hf * (int64_t)gridDim.x : 0), w_end = nwt;
+  const int64_t w_step = (PAIR ? 2 : 1) * (int64_t)gridDim.x;
+  if (SG) {                                                    // the workgroup's rounds blockIdx.x + i gridDim.x, split DF_SG_SHARE0 : the rest between the subgroups
     const int64_t n_wg = (int64_t)blockIdx.x < nwt ? (nwt - 1 - blockIdx.x) / w_step + 1 : 0;
     const int64_t n0 = (n_wg * DF_SG_SHARE0 + 16) >> 5;
     w_first = blockIdx.x + (sg ? n0 : 0) * w_step;
@@ -257,45 +297,67 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
   }
   // The rows of the next THREE rounds are in flight while a round computes: the workgroup is alone on its CU (LDS) and a round's rows
   // are only ~19 KB, so one round of look-ahead left the kernel bound by memory latency (19 KB per ~3 us per CU = 1.3 TB/s over the chip).
+  // (WT: TWO rounds, z1 / t1 stay unused)
+  constexpr int AHEAD = WT ? 2 : 3;
   LQTile<TT, NFZ> zt, z1, z2, zn;
   LQTile<TT, 2> tt, t1, t2, tn;
   auto fetch = [&](LQTile<TT, NFZ>& zz, LQTile<TT, 2>& tg, int64_t w) {
     const int64_t wc = w < nwt ? w : (nwt - 1);
-    const int64_t r0 = wc * R + prow;
+    const int64_t r0 = wc * RR + rrow;
     const int64_t rc = r0 < P ? r0 : P - 1;
     lq_load<TT, NFZ>(zz, Z, rc, Cz, kc, fastz);
     lq_load<TT, 2>(tg, TGT, rc, DF_F, kc, true);
   };
   fetch(zt, tt, w_first);
-  fetch(z1, t1, w_first + w_step);
-  fetch(z2, t2, w_first + 2 * w_step);
-  for (int64_t wt = w_first; wt < w_end; wt += w_step) {
-    int64_t row = wt * R + prow;
+  if constexpr (AHEAD == 3) {
+    fetch(z1, t1, w_first + w_step);
+    fetch(z2, t2, w_first + 2 * w_step);
+  } else {
+    fetch(z2, t2, w_first + w_step);
+  }
+  for (int64_t wt = w_first; wt - (PAIR ? hf * (int64_t)gridDim.x : 0) < w_end; wt += w_step) {
+    int64_t row = wt * RR + rrow;
     const bool inb = row < P;
     bool valid = inb;
     if (!inb) row = P - 1;
     if (valid && mask != nullptr) valid = mask[row] != 0;
-    fetch(zn, tn, wt + 3 * w_step);
+    fetch(zn, tn, wt + AHEAD * w_step);
     float h[32], xh[16];
     LQTile<TT, 4> ht;
-    dec_chain<NFZ>(h, xh, zt, w1, w2, b1q, b2q, ht, lane);
+    dec_chain<NFZ>(h, xh, zt, w1, w2, b1q, b2q, ht, lane, lane2);
     LQTile<TT, 2> dxt;
     const float kv = valid ? ksc : 0.f;
-    if constexpr (LOSS) {
-      if (valid) {
+    float d[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) { const float d = xh[j] - (float)tt.f[j >> 3][j & 7]; sq = fmaf(d, d, sq); }
+    for (int j = 0; j < 16; ++j) d[j] = xh[j] - (float)tt.f[j >> 3][j & 7];
+    if constexpr (LOSS) {                                       // no branch: a masked row adds +0, which leaves sq bit for bit what it was
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { const float dm = valid ? d[j] : 0.f; if (!PAIR || hf == 0) sq = fmaf(dm, dm, sq); }
+      if constexpr (PAIR) {
+        float* xch = reinterpret_cast<float*>(t_h + (wave & 3) * 16 * PH);
+        if (hf) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) xch[j * 64 + lane] = valid ? d[j] : 0.f;
+        }
+        __syncthreads();
+        if (!hf) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) { const float db = xch[j * 64 + lane]; sq = fmaf(db, db, sq); }
+        }
       }
       nrow += __popcll(__ballot(valid));                        // (each lane of a valid row holds 16 of its 64 elements)
     }
 #pragma unroll
-    for (int j = 0; j < 16; ++j) dxt.f[j >> 3][j & 7] = (bf16)(kv * (xh[j] - (float)tt.f[j >> 3][j & 7]));
+    for (int j = 0; j < 16; ++j) dxt.f[j >> 3][j & 7] = (bf16)(kv * d[j]);
     f32x4 dhacc[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
       dhacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int s = 0; s < 2; ++s) dhacc[m] = mfma16(w2t[(m * 2 + s) * 64 + lane], dxt.f[s], dhacc[m]);
+      for (int s = 0; s < 2; ++s) {
+        if constexpr (WT) dhacc[m] = mfma16(df_w2t_frag(w2tr + (8 * s + (m >> 1)) * 1024 + 8 * (m & 1)), dxt.f[s], dhacc[m]);
+        else dhacc[m] = mfma16(w2t[(m * 2 + s) * 64 + lane], dxt.f[s], dhacc[m]);
+      }
     }
     LQTile<TT, 4> dht;
 #pragma unroll
@@ -310,13 +372,15 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
     if (inb) {
       constexpr int QZ = 4 * CB;                               // latent channels per lane quarter
       TT* dzp = DZ + row * (int64_t)Cz + QZ * kc;
-      if (fastz) {
+      if (QZ >= 8 && fastz) {
+        if constexpr (QZ >= 8) {
 #pragma unroll
-        for (int j = 0; j < QZ; j += 8) {
-          bf16x8 o;
+          for (int j = 0; j < QZ; j += 8) {
+            bf16x8 o;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (bf16)dzacc[(j + e) >> 2][(j + e) & 3];
-          *reinterpret_cast<bf16x8*>(dzp + j) = o;
+            for (int e = 0; e < 8; ++e) o[e] = (bf16)dzacc[(j + e) >> 2][(j + e) & 3];
+            *reinterpret_cast<bf16x8*>(dzp + j) = o;
+          }
         }
       } else if ((Cz & 3) == 0) {                              // 12-channel latent rows: 8-byte stores
 #pragma unroll
@@ -355,8 +419,13 @@ __global__ __launch_bounds__(SG ? 512 : 64 * NW) void dec_mse_bwd_kernel(const T
       }
     }
     if constexpr (SG) df_sg_sync(bar, bgen, lane); else __syncthreads();
-    zt = z1; z1 = z2; z2 = zn;
-    tt = t1; t1 = t2; t2 = tn;
+    if constexpr (AHEAD == 3) {
+      zt = z1; z1 = z2; z2 = zn;
+      tt = t1; t1 = t2; t2 = tn;
+    } else {
+      zt = z2; z2 = zn;
+      tt = t2; t2 = tn;
+    }
   }
   float* my = slab + (int64_t)(SG ? 2 * blockIdx.x + sg : blockIdx.x) * (DF_F * DF_H + DF_H * CZP + DF_F + DF_H);   // (SG: a slab per subgroup)
 #pragma unroll
@@ -434,9 +503,8 @@ __global__ __launch_bounds__(256) void dec_mask_count_kernel(const uint8_t* __re
   }
 }
 
-template <int NFZ>
+template <int NFZ, int CB>
 __global__ void dec_pack_kernel(frag8* __restrict__ dst, const float* __restrict__ W1, const float* __restrict__ W2, int Cz, int bwd) {
-  constexpr int CZP = 32 * NFZ, CB = CZP / 16;
   const int tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
   pack_weights_lds<TT, NFZ>(dst, W1, DF_H, Cz, 8, Cz, 1, tid, nt);                       // hidden[o] = sum_i W1[o][i] z[i]
   frag8* p = dst + 8 * NFZ * 64;
@@ -449,9 +517,8 @@ __global__ void dec_pack_kernel(frag8* __restrict__ dst, const float* __restrict
 }
 
 // Packed image of the decoder weights (layout of dec_pack_kernel): from the caller's image cache when one is active, else packed into `ws_pk`.
-template <int NFZ>
+template <int NFZ, int CB = 2 * NFZ>
 static const frag8* dec_packed(const float* w1, const float* w2, int Cz, int bwd, frag8* ws_pk, hipStream_t st) {
-  constexpr int CZP = 32 * NFZ, CB = CZP / 16;
   FrlPackJob jobs[4];
   size_t off = 0;
   jobs[0] = frl_pack_job_pw(w1, off, FRL_BF16, NFZ, DF_H, Cz, 8, Cz, 1);
@@ -469,7 +536,7 @@ static const frag8* dec_packed(const float* w1, const float* w2, int Cz, int bwd
   bool hit = false;
   frag8* pk = ws_pk;
   if (void* img = frl_pack_cached(jobs, n, off, &hit)) pk = (frag8*)img;
-  if (!hit) FRL_LAUNCH((dec_pack_kernel<NFZ>), dim3(32), dim3(256), 0, st, pk, w1, w2, Cz, bwd);
+  if (!hit) FRL_LAUNCH((dec_pack_kernel<NFZ, CB>), dim3(32), dim3(256), 0, st, pk, w1, w2, Cz, bwd);
   return pk;
 }
 
@@ -478,17 +545,18 @@ static unsigned df_fwd_grid(int64_t P) { int64_t g = ((P + 15) / 16 + 3) / 4; if
 static unsigned df_bwd_grid(int64_t P, int R) { int64_t g = (P + R - 1) / R; if (g > 256) g = 256; return (unsigned)(g < 1 ? 1 : g); }
 
 // LOSS (one pass): the slabs are left unreduced in `ws` (frl_decoder_mse_reduce), *nslab_out receives their number
-template <int NFZ, int NW, bool LOSS = false>
+template <int NFZ, int NW, bool LOSS = false, int CB = 2 * NFZ>
 static int launch_dec_bwd(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* tgt,
                           const uint8_t* mask, const float* gscale, const float* stats, void* dz, float* dw1, float* db1, float* dw2,
                           float* db2, int64_t P, int Cz, char* ws, hipStream_t st, DecLoss<LOSS> la = DecLoss<LOSS>{}, int* nslab_out = nullptr) {
-  constexpr int CZP = 32 * NFZ, CB = CZP / 16, R = 16 * NW;
-  const unsigned grid = df_bwd_grid(P, R);
+  constexpr int CZP = 32 * NFZ, R = 16 * NW;
+  constexpr bool PAIR = NFZ == 2 && NW == 8;                   // the grid (and the slabs) of <2, 4>, no w2t image in the LDS
+  const unsigned grid = df_bwd_grid(P, PAIR ? 64 : R);
   const size_t slab_n = (size_t)DF_F * DF_H + DF_H * CZP + DF_F + DF_H;
-  const frag8* pk = dec_packed<NFZ>(w1, w2, Cz, 1, reinterpret_cast<frag8*>(ws + ((grid * slab_n * sizeof(float) + 255) / 256) * 256), st);
-  const size_t lds = (size_t)(8 * NFZ + 16 + 16 + CB * 4) * 64 * sizeof(frag8) + 192 * sizeof(float) +
+  const frag8* pk = dec_packed<NFZ, CB>(w1, w2, Cz, 1, reinterpret_cast<frag8*>(ws + ((grid * slab_n * sizeof(float) + 255) / 256) * 256), st);
+  const size_t lds = (size_t)(8 * NFZ + 16 + (PAIR ? 0 : 16) + CB * 4) * 64 * sizeof(frag8) + 192 * sizeof(float) +
                      (size_t)R * ((DF_F + 8) + 2 * (DF_H + 8) + (CZP + 8)) * sizeof(TT);
-  auto kern = dec_mse_bwd_kernel<NFZ, NW, false, LOSS>;
+  auto kern = dec_mse_bwd_kernel<NFZ, NW, false, LOSS, CB>;
   FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   FRL_LAUNCH_AS(LOSS ? "dec_mse_bwd_loss_kernel" : "dec_mse_bwd_kernel", kern, dim3(grid), dim3(64 * NW), lds, st, (const TT*)z, (const frag8*)pk, b1, b2, (const TT*)tgt, mask, gscale, stats, (TT*)dz, P, Cz,
              (float*)ws, la);
@@ -502,20 +570,21 @@ static int launch_dec_bwd(const void* z, const float* w1, const float* b1, const
 }
 
 // two independent 4-wave subgroups per workgroup (64-row tiles each), a slab per subgroup
-template <int NFZ, bool LOSS = false>
+template <int NFZ, bool LOSS = false, int CB = 2 * NFZ>
 static int launch_dec_bwd_sg(const void* z, const float* w1, const float* b1, const float* w2, const float* b2, const void* tgt,
                              const uint8_t* mask, const float* gscale, const float* stats, void* dz, float* dw1, float* db1, float* dw2,
                              float* db2, int64_t P, int Cz, char* ws, hipStream_t st, DecLoss<LOSS> la = DecLoss<LOSS>{}, int* nslab_out = nullptr) {
-  constexpr int CZP = 32 * NFZ, CB = CZP / 16, R = 64;
+  constexpr int CZP = 32 * NFZ, R = 64;
+  constexpr int NIMG = 8 * NFZ + 16 + 16 + CB * 4;
   int64_t g = (P + 2 * R - 1) / (2 * R);
   if (g > 256) g = 256;
   if (g < 1) g = 1;
   const unsigned grid = (unsigned)g, nslab = 2 * grid;
   const size_t slab_n = (size_t)DF_F * DF_H + DF_H * CZP + DF_F + DF_H;
-  const frag8* pk = dec_packed<NFZ>(w1, w2, Cz, 1, reinterpret_cast<frag8*>(ws + ((nslab * slab_n * sizeof(float) + 255) / 256) * 256), st);
-  const size_t lds = (size_t)(8 * NFZ + 16 + 16 + CB * 4) * 64 * sizeof(frag8) + (192 + 32) * sizeof(float) +
+  const frag8* pk = dec_packed<NFZ, CB>(w1, w2, Cz, 1, reinterpret_cast<frag8*>(ws + ((nslab * slab_n * sizeof(float) + 255) / 256) * 256), st);
+  const size_t lds = (size_t)NIMG * 64 * sizeof(frag8) + (192 + 32) * sizeof(float) +
                      (size_t)2 * R * ((DF_F + 8) + 2 * (DF_H + 8) + (CZP + 8)) * sizeof(TT);
-  auto kern = dec_mse_bwd_kernel<NFZ, 4, true, LOSS>;
+  auto kern = dec_mse_bwd_kernel<NFZ, 4, true, LOSS, CB>;
   FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   FRL_LAUNCH_AS(LOSS ? "dec_mse_bwd_sg_loss_kernel" : "dec_mse_bwd_sg_kernel", kern, dim3(grid), dim3(512), lds, st, (const TT*)z, (const frag8*)pk, b1, b2, (const TT*)tgt, mask, gscale, stats, (TT*)dz, P,
                 Cz, (float*)ws, la);
@@ -581,11 +650,16 @@ int frl_decoder_mse_bwd(const void* z, const float* w1, const float* b1, const f
   if (P <= 0) return frl_fail(-2, "decoder_mse_bwd: empty input");
   if (Cz < 1 || Cz > 64) return frl_fail(-2, "decoder_mse_bwd: latent width must be 1..64");
   if (ws_bytes < frl_decoder_mse_workspace_bytes(P, Cz)) return frl_fail(-4, "decoder_mse_bwd: workspace too small");
-  // (latents of more than 32 channels: the two subgroups' tiles do not fit the LDS beside the four weight images: 172 KB)
-  if (g_dec_subgroups && P >= 128 && Cz <= 32)
-    return launch_dec_bwd_sg<1>(z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream);
-  if (Cz <= 32) return launch_dec_bwd<1, 8>(z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream);
-  return launch_dec_bwd<2, 4>(z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream);
+#define DF_BWD_ARGS z, w1, b1, w2, b2, target, mask, gscale, stats, dz, dw1, db1, dw2, db2, P, Cz, (char*)ws, stream
+  if (g_dec_subgroups && P >= 128) {
+    if (Cz <= 16) return launch_dec_bwd_sg<1, false, 1>(DF_BWD_ARGS);
+    if (Cz <= 32) return launch_dec_bwd_sg<1>(DF_BWD_ARGS);
+    return launch_dec_bwd<2, 8>(DF_BWD_ARGS);
+  }
+  if (Cz <= 16) return launch_dec_bwd<1, 8, false, 1>(DF_BWD_ARGS);
+  if (Cz <= 32) return launch_dec_bwd<1, 8>(DF_BWD_ARGS);
+  return launch_dec_bwd<2, 4>(DF_BWD_ARGS);
+#undef DF_BWD_ARGS
 }
 
 // ---- one pass (train step) ----
@@ -617,11 +691,16 @@ int frl_decoder_mse_fwd_bwd(const void* z, const float* w1, const float* b1, con
     FRL_LAUNCH(dec_mask_count_kernel, dim3((unsigned)g), dim3(256), 0, stream, mask, P, c, out);
     la.nv_host = -1.f;
   }
-  if (g_dec_subgroups && P >= 128 && Cz <= 32)
-    return launch_dec_bwd_sg<1, true>(z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab);
-  if (Cz <= 32)
-    return launch_dec_bwd<1, 8, true>(z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab);
-  return launch_dec_bwd<2, 4, true>(z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab);
+#define DF_ONE_ARGS z, w1, b1, w2, b2, target, mask, gscale, nullptr, dz, nullptr, nullptr, nullptr, nullptr, P, Cz, (char*)buf, stream, la, nslab
+  if (g_dec_subgroups && P >= 128) {
+    if (Cz <= 16) return launch_dec_bwd_sg<1, true, 1>(DF_ONE_ARGS);
+    if (Cz <= 32) return launch_dec_bwd_sg<1, true>(DF_ONE_ARGS);
+    return launch_dec_bwd<2, 8, true>(DF_ONE_ARGS);
+  }
+  if (Cz <= 16) return launch_dec_bwd<1, 8, true, 1>(DF_ONE_ARGS);
+  if (Cz <= 32) return launch_dec_bwd<1, 8, true>(DF_ONE_ARGS);
+  return launch_dec_bwd<2, 4, true>(DF_ONE_ARGS);
+#undef DF_ONE_ARGS
 }
 
 // The slab reduction of a one-pass call: buf / nslab from frl_decoder_mse_fwd_bwd -> dw1 [128][Cz], db1 [128], dw2 [64][128], db2 [64], in the
