@@ -223,7 +223,3 @@ __global__ void tcn_pack_kernel(typename DT<T>::frag_t* __restrict__ dst, int mo
   }
   if (Wp != nullptr) pack_weights_lds<T, NFP>(p, Wp, Cout, Cp, MBO, pso, psi, tid, nt);
 }
-
-// per-channel constants of a lane quarter live in LDS ([4*Q] floats each) and are re-read when needed instead of
-// occupying Q registers each for the whole kernel
-__device__ __forceinline__ float lds_chan(const float* __restrict__ tab, int Q, int kc, int j) { return tab[Q * kc + j]; }
