@@ -526,6 +526,41 @@ int frl_evt_soft_nbr_bwd(const void* emb, int emb_dtype, int64_t N, int D, const
                          const int32_t* seg, const int32_t* seg_host, int nseg, float inv_tau_ref, float inv_tau_learned, const float* rowstat,
                          const float* segout, const float* gup, const float* seg_weights, void* grad, frl_stream_t stream);
 
+/* ---- phase margin losses (csrc/phase_margin.hip) ------------------------------------------------------------------------------
+ * The two remaining losses of the reference's cross-batch phase block (frl/training/representation/step.py:969-1006).  Distances are
+ * d = |a - b|_2 from exact differences with a compensated float32 sum of squares; softplus is torch's (x > 20 ? x : log1p(exp(x))).
+ * Recovery discrimination (phase_recovery_discrimination_loss, frl/losses/triplet_phase.py:352-426): z [N][T][D] (dtype 0 = float32,
+ * 1 = bfloat16), ysfc [N][T] f32 (NaN, infinite or negative = invalid).  Per pixel low[t] = valid && ysfc <= low_ysfc_max, high[t] =
+ * valid && ysfc >= high_ysfc_min, pairs = {(tl, th): low[tl] && high[th]}, d = sqrt(max(|z_tl - z_th|^2, 1e-12)),
+ * loss = sum softplus(margin - d) / n_pairs over all pixels and pairs (0 without pairs).  partial [N][2] f32 = per-pixel sum, pair count;
+ * out2 [2] = loss, n_pairs;  stats [4] doubles = loss, n_pairs, active pixels (both classes present), 0.  frl_recovery_disc_bwd recomputes
+ * the distances and writes grad [N][T][D] in z's dtype = gup[0] (device float) * d loss / d z, every row once (zeros for inactive pixels,
+ * without pairs, and from pairs whose sum of squares is under the clamp).  T <= 32, D <= 256.
+ * Spread ranking (compute_phase_spread_ranking, frl/losses/phase_neighborhood.py:637-740): per pair b, n_b = max(1, unmasked entries),
+ * spread_i = sum mask d_i / n_b, spread_j likewise, r_b = ref_diff [B] f32, term_b = softplus(spread_j - spread_i + margin) [r_b > delta]
+ * + softplus(spread_i - spread_j + margin) [r_b < -delta], loss = sum term_b / B.  pairstat [B][3] = spread_i, spread_j, n_b;  out2 [2] =
+ * loss, B;  stats [8] doubles = loss, pairs constrained with i the more dynamic, with j, satisfied constraints, sum spread_i, sum
+ * spread_j, sum |r_b|, B.  Matrix form: d_i, d_j [B][M][M] f32, mask [B][M][M] bytes, any M >= 1; frl_spread_rank_bwd writes
+ * grad_i = gup[0] c_b / (B n_b) on the unmasked entries (c_b = d term_b / d spread_i, 0 elsewhere) and grad_j = -grad_i.  Gathered form:
+ * the blocks are the self-distances of the rows emb[rows_i[b][t]] and emb[rows_j[b][t]] of emb [R][D] (dtype 0 / 1), mask = t, t' < K_b
+ * (lengths [B] int64, clamped into [0, M]) and t != t'; the [B][M] int64 index arrays must lie in [0, R); M <= 32, D <= 256.
+ * frl_spread_rank_gathered_bwd writes grad_rows [2][B][M][D] f32 (role i, then role j; zero where a distance is zero, beyond K_b and
+ * for unconstrained pairs) for frl_segment_sum_rows to fold into d emb.  Fixed reduction order, no float atomics: bit-reproducible. */
+int frl_recovery_disc_fwd(const void* z, int dtype, const float* ysfc, int64_t N, int T, int D, float margin, float low_ysfc_max,
+                          float high_ysfc_min, float* partial, float* out2, double* stats, frl_stream_t stream);
+int frl_recovery_disc_bwd(const void* z, int dtype, const float* ysfc, int64_t N, int T, int D, float margin, float low_ysfc_max,
+                          float high_ysfc_min, const float* out2, const float* gup, void* grad, frl_stream_t stream);
+int frl_spread_rank_fwd(const float* d_i, const float* d_j, const unsigned char* mask, const float* ref_diff, int64_t B, int M, float margin,
+                        float delta, float* pairstat, float* out2, double* stats, frl_stream_t stream);
+int frl_spread_rank_bwd(const unsigned char* mask, const float* pairstat, const float* ref_diff, const float* gup, int64_t B, int M,
+                        float margin, float delta, float* grad_i, float* grad_j, frl_stream_t stream);
+int frl_spread_rank_gathered_fwd(const void* emb, int D, int emb_dtype, const int64_t* rows_i, const int64_t* rows_j, const int64_t* lengths,
+                                 const float* ref_diff, int64_t B, int M, float margin, float delta, float* pairstat, float* out2,
+                                 double* stats, frl_stream_t stream);
+int frl_spread_rank_gathered_bwd(const void* emb, int D, int emb_dtype, const int64_t* rows_i, const int64_t* rows_j, const int64_t* lengths,
+                                 const float* ref_diff, int64_t B, int M, float margin, float delta, const float* pairstat, const float* gup,
+                                 float* grad_rows, frl_stream_t stream);
+
 /* ---- code-map decoding (csrc/codes.hip) --------------------------------------------------------------------------------------
  * frl_decode_codes: out[p][:] = table[idx[p]][:] for a decoded-code table [K][F] (dtype 0 = float32, 1 = bfloat16; the VQ-VAE decoder
  * applied to the K codebook rows), idx [P] int32.  Indices in [-K, 0) wrap to idx + K; any other out-of-range index is clamped into

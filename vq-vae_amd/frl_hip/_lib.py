@@ -159,6 +159,12 @@ SIGNATURES = {
     "frl_soft_nbr_gathered_bwd": (c_int, [P, I, P, I, I, P, P, P, P, P, P, L, I, I, F, F, I, P, P, P, P, P]),
     "frl_evt_soft_nbr_fwd": (c_int, [P, I, L, I, P, P, P, I, P, P, I, F, F, I, P, P, P, P, P]),
     "frl_evt_soft_nbr_bwd": (c_int, [P, I, L, I, P, P, P, I, P, P, I, F, F, P, P, P, P, P, P]),
+    "frl_recovery_disc_fwd": (c_int, [P, I, P, L, I, I, F, F, F, P, P, P, P]),
+    "frl_recovery_disc_bwd": (c_int, [P, I, P, L, I, I, F, F, F, P, P, P, P]),
+    "frl_spread_rank_fwd": (c_int, [P, P, P, P, L, I, F, F, P, P, P, P]),
+    "frl_spread_rank_bwd": (c_int, [P, P, P, P, L, I, F, F, P, P, P]),
+    "frl_spread_rank_gathered_fwd": (c_int, [P, I, I, P, P, P, P, L, I, F, F, P, P, P, P]),
+    "frl_spread_rank_gathered_bwd": (c_int, [P, I, I, P, P, P, P, L, I, F, F, P, P, P, P]),
 }
 
 

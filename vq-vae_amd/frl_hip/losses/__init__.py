@@ -4,3 +4,5 @@ from .variance_covariance import variance_covariance_loss, variance_loss, covari
 from .soft_neighborhood import (soft_neighborhood_matching_loss, soft_neighborhood_loss_gathered, phase_alignment,  # noqa: F401
                                 phase_neighborhood_loss)
 from .evt_soft_neighborhood import EvtDiffusionMetric, evt_soft_neighborhood_loss, evt_soft_neighborhood_loss_batched  # noqa: F401
+from .phase_margin import (phase_recovery_discrimination_loss, compute_phase_spread_ranking, phase_spread_ranking_gathered,  # noqa: F401
+                           phase_spread_ranking_loss)

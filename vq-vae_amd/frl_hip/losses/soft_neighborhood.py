@@ -57,16 +57,20 @@ class _GatheredFn(Function):
         exclude_diagonal, tau_ref, tau_learned, min_valid = ctx.hp
         grows = ops.soft_nbr_gathered_bwd(ref, emb, rows, lengths, exclude_diagonal, weights, tau_ref, tau_learned, min_valid, pairstat, out2,
                                           g.reshape(1).float().contiguous(), checked=True)
-        # role a's rows ahead of role b's, each in pair order, grouped by embedding row (stable sort: index plumbing) and summed in that order.
-        # Positions beyond lengths carry zero rows and whatever index the caller padded with (phase_alignment: 0); keyed by that they would
-        # form one long run that a single thread walks, so they are dealt round the embedding rows instead (adding zeros, no host read).
-        keys = rows[2:]
-        inside = torch.arange(keys.shape[2], device=keys.device) < lengths.unsqueeze(1)
-        dealt = torch.arange(keys.numel(), device=keys.device).reshape(keys.shape) % emb.shape[0]
-        keys, order = torch.sort(torch.where(inside, keys, dealt).reshape(-1), stable=True)
-        de = torch.zeros(emb.shape, dtype=torch.float32, device=emb.device)
-        ops.segment_sum_rows(grows.reshape(-1, emb.shape[1]), order, keys, de)
-        return de.to(emb.dtype), None, None, None, None, None, None, None, None
+        return _fold_gradient_rows(grows, rows[2:], lengths, emb), None, None, None, None, None, None, None, None
+
+
+def _fold_gradient_rows(grows, keys, lengths, emb):
+    """grows [2, B, M, D] float32 gradient rows of the positions keys [2, B, M] (rows of emb) -> d emb in emb's dtype."""
+    # role a's rows ahead of role b's, each in pair order, grouped by embedding row (stable sort: index plumbing) and summed in that order.
+    # Positions beyond lengths carry zero rows and whatever index the caller padded with (phase_alignment: 0); keyed by that they would
+    # form one long run that a single thread walks, so they are dealt round the embedding rows instead (adding zeros, no host read).
+    inside = torch.arange(keys.shape[2], device=keys.device) < lengths.unsqueeze(1)
+    dealt = torch.arange(keys.numel(), device=keys.device).reshape(keys.shape) % emb.shape[0]
+    keys, order = torch.sort(torch.where(inside, keys, dealt).reshape(-1), stable=True)
+    de = torch.zeros(emb.shape, dtype=torch.float32, device=emb.device)
+    ops.segment_sum_rows(grows.reshape(-1, emb.shape[1]), order, keys, de)
+    return de.to(emb.dtype)
 
 
 def _weights(pair_weights: Optional[torch.Tensor], b: int, device) -> Optional[torch.Tensor]:

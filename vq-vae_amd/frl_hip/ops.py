@@ -1598,3 +1598,168 @@ def evt_soft_nbr_bwd(emb: torch.Tensor, idx: torch.Tensor, table: torch.Tensor, 
                                            1.0 / float(tau_ref), 1.0 / float(tau_learned), _p(rowstat), _p(segout), _p(gup), _p(seg_weights),
                                            _p(grad), _stream()), "frl_evt_soft_nbr_bwd")
     return grad
+
+
+# ----------------------------------------------------------------------------------------------
+# phase margin losses: recovery discrimination and spread ranking (csrc/phase_margin.hip)
+# ----------------------------------------------------------------------------------------------
+PHASE_MARGIN_MAX_T, PHASE_MARGIN_MAX_WIDTH = 32, 256
+
+
+def _chk_recovery_disc(name: str, z: torch.Tensor, ysfc: torch.Tensor):
+    """Shape limits first (they hold on any device), then the device, then the layouts -> (N, T, D)."""
+    if z.dim() != 3 or ysfc.dim() != 2 or tuple(ysfc.shape) != tuple(z.shape[:2]):
+        raise ValueError(f"{name}: expected z [N, T, D] and ysfc [N, T], got {tuple(z.shape)} and {tuple(ysfc.shape)}")
+    n, t, d = z.shape
+    if t > PHASE_MARGIN_MAX_T:
+        raise ValueError(f"{name}: supports T <= {PHASE_MARGIN_MAX_T} timesteps, got T = {t}")
+    if d > PHASE_MARGIN_MAX_WIDTH:
+        raise ValueError(f"{name}: supports D <= {PHASE_MARGIN_MAX_WIDTH}, got D = {d}")
+    if not (z.is_cuda and ysfc.is_cuda):
+        raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+    if n < 1 or t < 1 or d < 1:
+        raise ValueError(f"{name}: needs at least one pixel, timestep and column")
+    if z.dtype not in (torch.float32, torch.bfloat16) or not z.is_contiguous():
+        raise ValueError(f"{name}: z must be a contiguous float32 or bfloat16 tensor")
+    if ysfc.dtype != torch.float32 or not ysfc.is_contiguous() or ysfc.device != z.device:
+        raise ValueError(f"{name}: ysfc must be a contiguous float32 [{n}, {t}] tensor on the device of z")
+    return n, t, d
+
+
+@_timed("recovery_disc_fwd")
+def recovery_disc_fwd(z: torch.Tensor, ysfc: torch.Tensor, margin: float = 0.5, low_ysfc_max: float = 1.0, high_ysfc_min: float = 5.0):
+    """z [N, T, D] float32 | bfloat16, ysfc [N, T] float32 (NaN / negative = invalid) -> (out2 f32 [2] = loss, n_pairs; stats f64 [4] =
+    loss, n_pairs, active pixels, 0).  T <= 32, D <= 256."""
+    n, t, d = _chk_recovery_disc("recovery_disc_fwd", z, ysfc)
+    partial = torch.empty(n, 2, dtype=torch.float32, device=z.device)
+    out2 = torch.empty(2, dtype=torch.float32, device=z.device)
+    stats = torch.empty(4, dtype=torch.float64, device=z.device)
+    check(_lib.load().frl_recovery_disc_fwd(_p(z), _dt(z), _p(ysfc), n, t, d, float(margin), float(low_ysfc_max), float(high_ysfc_min),
+                                            _p(partial), _p(out2), _p(stats), _stream()), "frl_recovery_disc_fwd")
+    return out2, stats
+
+
+@_timed("recovery_disc_bwd")
+def recovery_disc_bwd(z: torch.Tensor, ysfc: torch.Tensor, margin: float, low_ysfc_max: float, high_ysfc_min: float, out2: torch.Tensor,
+                      g: torch.Tensor) -> torch.Tensor:
+    """d z [N, T, D] in z's dtype for the outputs of recovery_disc_fwd, every row written; g: float32 [1] on the device."""
+    n, t, d = _chk_recovery_disc("recovery_disc_bwd", z, ysfc)
+    for x, shape, name in ((out2, (2,), "out2"), (g, (1,), "g")):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != z.device:
+            raise ValueError(f"recovery_disc_bwd: {name} must be a contiguous float32 {shape} tensor on the device of z")
+    grad = torch.empty_like(z)
+    check(_lib.load().frl_recovery_disc_bwd(_p(z), _dt(z), _p(ysfc), n, t, d, float(margin), float(low_ysfc_max), float(high_ysfc_min),
+                                            _p(out2), _p(g), _p(grad), _stream()), "frl_recovery_disc_bwd")
+    return grad
+
+
+def _spread_rank_outputs(b: int, device):
+    return (torch.empty(b, 3, dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
+            torch.empty(8, dtype=torch.float64, device=device))
+
+
+def _chk_spread_ref_diff(name: str, ref_diff: torch.Tensor, b: int, device):
+    if ref_diff.dtype != torch.float32 or tuple(ref_diff.shape) != (b,) or not ref_diff.is_contiguous() or ref_diff.device != device:
+        raise ValueError(f"{name}: ref_diff must be a contiguous float32 [{b}] tensor on the device of the inputs")
+
+
+def _chk_spread_rank(name: str, mask: torch.Tensor, ref_diff: torch.Tensor, blocks):
+    if mask.dim() != 3 or mask.shape[1] != mask.shape[2] or any(x.shape != mask.shape for x in blocks):
+        raise ValueError(f"{name}: expected distance blocks and mask of one shape [B, M, M], got {[tuple(x.shape) for x in blocks]} and "
+                         f"{tuple(mask.shape)}")
+    if tuple(ref_diff.shape) != (mask.shape[0],):
+        raise ValueError(f"{name}: ref_diff must have shape [{mask.shape[0]}], got {tuple(ref_diff.shape)}")
+    if not (mask.is_cuda and ref_diff.is_cuda and all(x.is_cuda for x in blocks)):
+        raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+    b, m, _ = mask.shape
+    if b < 1 or m < 1:
+        raise ValueError(f"{name}: needs at least one pair and position")
+    if mask.dtype != torch.bool or not mask.is_contiguous():
+        raise ValueError(f"{name}: mask must be a contiguous bool tensor")
+    for x in blocks:
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != mask.device:
+            raise ValueError(f"{name}: the distance blocks must be contiguous float32 tensors on the device of mask")
+    _chk_spread_ref_diff(name, ref_diff, b, mask.device)
+    return b, m
+
+
+@_timed("spread_rank_fwd")
+def spread_rank_fwd(d_i: torch.Tensor, d_j: torch.Tensor, mask: torch.Tensor, ref_diff: torch.Tensor, margin: float = 0.1,
+                    delta: float = 0.5):
+    """d_i, d_j [B, M, M] float32, mask [B, M, M] bool, ref_diff [B] float32 -> (out2 f32 [2] = loss, B; stats f64 [8] = loss, constrained i,
+    constrained j, satisfied, sum spread_i, sum spread_j, sum |ref_diff|, B; pairstat f32 [B, 3] = spread_i, spread_j, n_b)."""
+    b, m = _chk_spread_rank("spread_rank_fwd", mask, ref_diff, (d_i, d_j))
+    pairstat, out2, stats = _spread_rank_outputs(b, mask.device)
+    check(_lib.load().frl_spread_rank_fwd(_p(d_i), _p(d_j), _p(mask), _p(ref_diff), b, m, float(margin), float(delta), _p(pairstat), _p(out2),
+                                          _p(stats), _stream()), "frl_spread_rank_fwd")
+    return out2, stats, pairstat
+
+
+@_timed("spread_rank_bwd")
+def spread_rank_bwd(mask: torch.Tensor, pairstat: torch.Tensor, ref_diff: torch.Tensor, margin: float, delta: float, g: torch.Tensor):
+    """(d loss / d d_i, d loss / d d_j) float32 [B, M, M] for the outputs of spread_rank_fwd; g: float32 [1] on the device."""
+    b, m = _chk_spread_rank("spread_rank_bwd", mask, ref_diff, ())
+    for x, shape, name in ((pairstat, (b, 3), "pairstat"), (g, (1,), "g")):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != mask.device:
+            raise ValueError(f"spread_rank_bwd: {name} must be a contiguous float32 {shape} tensor on the device of mask")
+    gi = torch.empty(b, m, m, dtype=torch.float32, device=mask.device)
+    gj = torch.empty_like(gi)
+    check(_lib.load().frl_spread_rank_bwd(_p(mask), _p(pairstat), _p(ref_diff), _p(g), b, m, float(margin), float(delta), _p(gi), _p(gj),
+                                          _stream()), "frl_spread_rank_bwd")
+    return gi, gj
+
+
+def _chk_spread_rank_gathered(name: str, emb, rows, lengths, ref_diff, checked: bool):
+    """Shape limits first, then the device, then the layouts -> (B, M, rows [2, B, M] inside [0, R))."""
+    if emb.dim() != 2:
+        raise ValueError(f"{name}: expected emb [R, D], got {tuple(emb.shape)}")
+    if rows.dim() != 3 or rows.shape[0] != 2:
+        raise ValueError(f"{name}: the row indices come stacked as [2, B, M] (role i, role j), got {tuple(rows.shape)}")
+    _, b, m = rows.shape
+    if m > PHASE_MARGIN_MAX_T:
+        raise ValueError(f"{name}: the gathered form supports M <= {PHASE_MARGIN_MAX_T} positions per pair, got M = {m}")
+    if emb.shape[1] > PHASE_MARGIN_MAX_WIDTH:
+        raise ValueError(f"{name}: the gathered form supports D <= {PHASE_MARGIN_MAX_WIDTH}, got D = {emb.shape[1]}")
+    if tuple(lengths.shape) != (b,) or tuple(ref_diff.shape) != (b,):
+        raise ValueError(f"{name}: lengths and ref_diff must have shape [{b}], got {tuple(lengths.shape)} and {tuple(ref_diff.shape)}")
+    if not (emb.is_cuda and rows.is_cuda and lengths.is_cuda and ref_diff.is_cuda):
+        raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+    if b < 1 or m < 1 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise ValueError(f"{name}: needs at least one pair, position, row and column")
+    if emb.dtype not in (torch.float32, torch.bfloat16) or not emb.is_contiguous():
+        raise ValueError(f"{name}: emb must be contiguous float32 or bfloat16 rows")
+    if rows.dtype != torch.int64 or not rows.is_contiguous() or lengths.dtype != torch.int64 or not lengths.is_contiguous():
+        raise ValueError(f"{name}: row indices [2, {b}, {m}] and lengths [{b}] must be contiguous int64")
+    _chk_spread_ref_diff(name, ref_diff, b, emb.device)
+    if not checked:
+        rows = sanitize_indices(rows, emb.shape[0], name + ": row indices")
+    return b, m, rows
+
+
+@_timed("spread_rank_gathered_fwd")
+def spread_rank_gathered_fwd(emb: torch.Tensor, rows: torch.Tensor, lengths: torch.Tensor, ref_diff: torch.Tensor, margin: float = 0.1,
+                             delta: float = 0.5, checked: bool = False):
+    """emb [R, D] float32 | bfloat16, rows [2, B, M] int64 (role i, role j), lengths [B] int64, ref_diff [B] float32 -> (out2, stats,
+    pairstat as spread_rank_fwd, rows sanitised into [0, R)).  M <= 32, D <= 256."""
+    b, m, rows = _chk_spread_rank_gathered("spread_rank_gathered_fwd", emb, rows, lengths, ref_diff, checked)
+    pairstat, out2, stats = _spread_rank_outputs(b, emb.device)
+    check(_lib.load().frl_spread_rank_gathered_fwd(_p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(lengths), _p(ref_diff), b, m,
+                                                   float(margin), float(delta), _p(pairstat), _p(out2), _p(stats), _stream()),
+          "frl_spread_rank_gathered_fwd")
+    return out2, stats, pairstat, rows
+
+
+@_timed("spread_rank_gathered_bwd")
+def spread_rank_gathered_bwd(emb: torch.Tensor, rows: torch.Tensor, lengths: torch.Tensor, ref_diff: torch.Tensor, margin: float, delta: float,
+                             pairstat: torch.Tensor, g: torch.Tensor, checked: bool = False) -> torch.Tensor:
+    """Gradient rows float32 [2, B, M, D] (role i, then role j) for the outputs of spread_rank_gathered_fwd; fold them into d emb with
+    segment_sum_rows.  g: float32 [1] on the device."""
+    b, m, rows = _chk_spread_rank_gathered("spread_rank_gathered_bwd", emb, rows, lengths, ref_diff, checked)
+    for x, shape, name in ((pairstat, (b, 3), "pairstat"), (g, (1,), "g")):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != emb.device:
+            raise ValueError(f"spread_rank_gathered_bwd: {name} must be a contiguous float32 {shape} tensor on the device of emb")
+    grows = torch.empty(2, b, m, emb.shape[1], dtype=torch.float32, device=emb.device)
+    check(_lib.load().frl_spread_rank_gathered_bwd(_p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(lengths), _p(ref_diff), b, m,
+                                                   float(margin), float(delta), _p(pairstat), _p(g), _p(grows), _stream()),
+          "frl_spread_rank_gathered_bwd")
+    return grows
