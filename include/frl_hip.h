@@ -430,6 +430,8 @@ int frl_vq_prepare(const float* E, int64_t N, int K, int d, int dtype, void* pre
 int frl_vq_assign_fwd_prepared(const void* z, const float* E, void* prep /* NULL: prepare inside the call */, int64_t N, int K, int d,
                                int32_t* idx_out, void* zq_out, float* stats_out, int32_t* counts_out, int dtype, void* ws,
                                size_t ws_bytes, frl_stream_t stream);
+/* Returns -2 for N, K or d <= 0, for bf16 rows with d > 128 (the widest matrix-core instance covers 128 channels, as the forward), and for
+ * float32 rows when one code row (d * 4 bytes) exceeds the 96 KiB LDS chunk. */
 int frl_vq_bwd(const void* g_out, const void* z, const void* zq /* optional */, const float* E, const int32_t* idx, const int32_t* counts,
                const float* gscale, float beta, int64_t N, int K, int d, void* g_z_out, float* g_E_out, float* sums_out,
                int dtype, void* ws, size_t ws_bytes, frl_stream_t stream);

@@ -2090,10 +2090,14 @@ int frl_vq_assign_fwd(const void* z, const float* E, int64_t N, int K, int d, in
 int frl_vq_bwd(const void* g_out, const void* z, const void* zq, const float* E, const int32_t* idx, const int32_t* counts,
                const float* gscale, float beta, int64_t N, int K, int d, void* g_z_out, float* g_E_out,
                float* sums_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
-  if (N <= 0) return frl_fail(-2, "vq_bwd: empty input");
+  if (N <= 0 || K <= 0 || d <= 0) return frl_fail(-2, "vq_bwd: empty input");
+  if (dtype != FRL_F32 && dtype != FRL_BF16) return frl_fail(-2, "vq_bwd: bad dtype");
+  // the widest matrix-core instance covers 128 channels (as the forward); the float32 kernel is generic in d up to one code per LDS chunk
+  if (dtype == FRL_BF16 && d > 128) return frl_fail(-2, "vq_bwd: d > 128 unsupported in bf16");
   if (ws_bytes < frl_vq_workspace_bytes(N, K, d)) return frl_fail(-4, "vq_bwd: workspace too small");
   const int Kc = vq_bwd_chunk(K, d);
   const size_t lds = (size_t)Kc * d * 4;
+  if (dtype == FRL_F32 && lds > 96 * 1024) return frl_fail(-2, "vq_bwd: one code row exceeds the LDS chunk");
   const int64_t rows = (N + VQ_BWD_WGS - 1) / VQ_BWD_WGS;
   const float cz = beta * 2.f / ((float)N * (float)d), ce = 2.f / ((float)N * (float)d);
   float* slab = (float*)ws;

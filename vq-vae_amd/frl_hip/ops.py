@@ -400,8 +400,29 @@ def vq_assign(z: torch.Tensor, codebook: torch.Tensor, prep: Optional[torch.Tens
 def vq_bwd(g_out: Optional[torch.Tensor], z: torch.Tensor, codebook: torch.Tensor, idx: torch.Tensor,
            counts: torch.Tensor, gscale: Optional[torch.Tensor], beta: float, want_gz: bool = True,
            want_ge: bool = True, want_sums: bool = False, zq: Optional[torch.Tensor] = None):
+    """g_z = g_out + gscale[0] beta 2/(N d) (z - e_idx), g_E = gscale[1] 2/(N d) (n_k e_k - S_k), S_k = per-code sums of z.  The kernels
+    read every operand as raw rows of z's dtype / int32 / float32, so anything else is refused here, before the launch."""
+    if codebook.dim() != 2:
+        raise ValueError(f"vq_bwd: codebook must be [K, d], got {tuple(codebook.shape)}")
     k, d = codebook.shape
+    if not z.is_cuda:
+        raise ValueError("vq_bwd.z: tensor must live on the GPU (no CPU fallback)")
+    if z.dim() < 1 or z.shape[-1] != d or not z.is_contiguous():
+        raise ValueError(f"vq_bwd.z: expected contiguous [..., {d}] rows, got {tuple(z.shape)} stride {z.stride()}")
     n = z.numel() // d
+    if g_out is not None:
+        _chk_like(g_out, z, "vq_bwd.g_out")
+    if zq is not None:
+        _chk_like(zq, z, "vq_bwd.zq")
+    for t, m, name in ((idx, n, "idx"), (counts, k, "counts")):
+        if t.dtype != torch.int32 or t.numel() != m or not t.is_contiguous() or t.device != z.device:
+            raise ValueError(f"vq_bwd.{name}: expected a contiguous int32 tensor of {m} elements on {z.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    if gscale is not None and (gscale.dtype != torch.float32 or gscale.device != z.device or gscale.numel() < 2
+                               or not gscale.is_contiguous()):
+        raise ValueError("vq_bwd.gscale: expected a contiguous float32 tensor of at least 2 elements on the device of z")
+    if codebook.device != z.device:
+        raise ValueError("vq_bwd: codebook and z live on different devices")
     lib = _lib.load()
     ws = workspace(lib.frl_vq_workspace_bytes(n, k, d), z.device)
     gz = torch.empty_like(z) if want_gz else None
