@@ -581,6 +581,25 @@ size_t frl_mutual_knn_max_points(int D);
 int frl_mutual_knn(const float* feat, int N, int D, const int32_t* patch_id, const float* coords, float pos_min_spatial, int k,
                    int32_t* knn_idx, uint8_t* mutual, frl_stream_t stream);
 
+/* ---- phase pair mining (csrc/phase_pairs.hip) ---------------------------------------------------------------------------------
+ * frl/losses/phase_pairs.py:74-253 build_phase_pairs for every segment (sample) of a batch in one launch pair.  spec [N][D] float32 with
+ * D in {16, 32, 48, 64, 96, 128, 256} (pad narrower features with zero columns), ysfc [N][T] float32, seg_host / seg: the S + 1 segment
+ * offsets rising from 0 to N on the host (checked, sizes the grid) and the same on the device (read by the kernel); segments may be empty.
+ * Per anchor i of segment s (n_s rows): the min(k, n_s - 1) nearest anchors of s by squared L2 (float32 sum of squared differences),
+ * never i itself, in ascending (distance, index); overlap = number of distinct trunc(ysfc) values in 0..255 both pixels carry;
+ * keep_overlap = overlap >= min_overlap; anchor_ok = at least min_pairs of its neighbours pass; keep = keep_overlap and anchor_ok;
+ * dist = sqrtf(squared distance), weight = expf(-dist / sigma).  1 <= k <= 64.
+ * out: knn_idx [N][k] int32 row numbers (-1 beyond n_s - 1 neighbours, where overlap, keep, keep_overlap, weight and dist are 0),
+ * overlap [N][k] int32, keep / keep_overlap [N][k] bytes, weight / dist [N][k] float32, anchor_ok [N] bytes; counters [S][4] int32
+ * (candidates, passing the overlap, cross pairs kept, anchors surviving) are ADDED to and *flag is OR-ed with 1 when ysfc holds a NaN, an
+ * infinity, a negative value or a value >= 256 (such a value sets no bit): the caller zeroes both.  masks: workspace of N * 4 64-bit words.
+ * A segment longer than frl_phase_pairs_max_points(D) (four distance rows share the LDS with the staging tile) returns -3. */
+size_t frl_phase_pairs_max_points(int D);
+int frl_phase_pairs(const float* spec, const float* ysfc, int N, int D, int T, const int32_t* seg_host, const int32_t* seg, int S, int k,
+                    int min_overlap, int min_pairs, float sigma, uint64_t* masks, int32_t* knn_idx, int32_t* overlap, uint8_t* keep,
+                    uint8_t* keep_overlap, float* weight, float* dist, uint8_t* anchor_ok, int32_t* counters, int32_t* flag,
+                    frl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,8 @@ SIGNATURES = {
     "frl_infonce_pair_grads": (c_int, [P, I, P, P, P, P, L, L, F, I, P, P, P]),
     "frl_mutual_knn_max_points": (S, [I]),
     "frl_mutual_knn": (c_int, [P, I, I, P, P, F, I, P, P, P]),
+    "frl_phase_pairs_max_points": (S, [I]),
+    "frl_phase_pairs": (c_int, [P, P, I, I, I, P, P, I, I, I, I, F] + [P] * 11),
     "frl_host_parallel_copy": (c_int, [P, P, S, I]),
     "frl_normalize_chunk_tiles": (c_int, [P, I, I, I, I, I, P, I, I, P, P, I, P, P]),
     "frl_conv3x3_fwd": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P, S, P]),

@@ -6,3 +6,4 @@ from .soft_neighborhood import (soft_neighborhood_matching_loss, soft_neighborho
 from .evt_soft_neighborhood import EvtDiffusionMetric, evt_soft_neighborhood_loss, evt_soft_neighborhood_loss_batched  # noqa: F401
 from .phase_margin import (phase_recovery_discrimination_loss, compute_phase_spread_ranking, phase_spread_ranking_gathered,  # noqa: F401
                            phase_spread_ranking_loss)
+from .phase_pairs import build_phase_pairs, build_phase_pairs_batched  # noqa: F401

@@ -766,6 +766,50 @@ def mutual_knn(features: torch.Tensor, patch_id: torch.Tensor, coords: torch.Ten
     return knn, mutual
 
 
+@_timed("phase_pairs")
+def phase_pairs(spec: torch.Tensor, ysfc: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor, k: int, min_overlap: int, min_pairs: int,
+                sigma: float):
+    """spec [N, D] float32, ysfc [N, T] float32, seg int32 [S + 1] row offsets on the device and seg_host the same on the host (validated
+    there) -> dict of knn_idx / overlap int32 [N, k], keep / keep_overlap uint8 [N, k], weight / dist float32 [N, k], anchor_ok uint8 [N]
+    and meta int32 [4 S + 1]: the [S, 4] counters (candidates, passing the overlap, cross pairs kept, anchors surviving) followed by the
+    invalid-ysfc flag.  include/frl_hip.h (frl_phase_pairs) has the definitions.  No host read."""
+    if spec.dim() != 2 or ysfc.dim() != 2 or ysfc.shape[0] != spec.shape[0] or spec.shape[0] == 0 or ysfc.shape[1] == 0:
+        raise ValueError(f"phase_pairs: expected spec [N, D] and ysfc [N, T] with N, T > 0, got {tuple(spec.shape)} and {tuple(ysfc.shape)}")
+    if not 1 <= int(k) <= 64:
+        raise ValueError(f"phase_pairs: k must be in 1..64 (one lane per neighbour), got {k}")
+    if not float(sigma) > 0.0:
+        raise ValueError(f"phase_pairs: sigma must be positive, got {sigma}")
+    n, d = spec.shape
+    if d > 256:
+        raise ValueError("phase_pairs: at most 256 feature channels")
+    if not spec.is_cuda or not ysfc.is_cuda:
+        raise _lib.FrlHipError("phase_pairs: tensors must live on the GPU (no CPU fallback)")
+    if spec.dtype != torch.float32 or ysfc.dtype != torch.float32 or not spec.is_contiguous() or not ysfc.is_contiguous() \
+            or ysfc.device != spec.device:
+        raise ValueError("phase_pairs: spec and ysfc must be contiguous float32 tensors on one device")
+    if seg_host.is_cuda or seg_host.dtype != torch.int32 or seg_host.dim() != 1 or seg_host.numel() < 2 or not seg_host.is_contiguous():
+        raise ValueError("phase_pairs: the host segment offsets must be a contiguous int32 [segments + 1] CPU tensor")
+    if seg.dtype != torch.int32 or seg.shape != seg_host.shape or not seg.is_contiguous() or seg.device != spec.device:
+        raise ValueError(f"phase_pairs: the device segment offsets must be a contiguous int32 [{seg_host.numel()}] tensor on the device of spec")
+    width = min(w for w in (16, 32, 48, 64, 96, 128, 256) if w >= d)     # the widths the kernel is compiled for
+    if width != d:
+        # zero columns add exactly nothing to a squared distance (and leave the summation order of the real ones untouched)
+        spec = torch.nn.functional.pad(spec, (0, width - d)).contiguous()
+        d = width
+    s, dev, k = seg_host.numel() - 1, spec.device, int(k)
+    out = {"knn_idx": torch.empty((n, k), dtype=torch.int32, device=dev), "overlap": torch.empty((n, k), dtype=torch.int32, device=dev),
+           "keep": torch.empty((n, k), dtype=torch.uint8, device=dev), "keep_overlap": torch.empty((n, k), dtype=torch.uint8, device=dev),
+           "weight": torch.empty((n, k), dtype=torch.float32, device=dev), "dist": torch.empty((n, k), dtype=torch.float32, device=dev),
+           "anchor_ok": torch.empty(n, dtype=torch.uint8, device=dev), "meta": torch.zeros(4 * s + 1, dtype=torch.int32, device=dev)}
+    masks = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    meta = out["meta"]
+    check(_lib.load().frl_phase_pairs(_p(spec), _p(ysfc), n, d, ysfc.shape[1], _p(seg_host), _p(seg), s, k, int(min_overlap), int(min_pairs),
+                                      float(sigma), _p(masks), _p(out["knn_idx"]), _p(out["overlap"]), _p(out["keep"]),
+                                      _p(out["keep_overlap"]), _p(out["weight"]), _p(out["dist"]), _p(out["anchor_ok"]), _p(meta),
+                                      ctypes.c_void_p(meta.data_ptr() + 16 * s), _stream()), "frl_phase_pairs")
+    return out
+
+
 @_timed("normalize_tiles")
 def normalize_tiles(raw: torch.Tensor, table: torch.Tensor, valid: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16,
                     out: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
