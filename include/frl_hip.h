@@ -600,6 +600,30 @@ int frl_phase_pairs(const float* spec, const float* ysfc, int N, int D, int T, c
                     uint8_t* keep_overlap, float* weight, float* dist, uint8_t* anchor_ok, int32_t* counters, int32_t* flag,
                     frl_stream_t stream);
 
+/* ---- type-local spectral baseline (csrc/type_baseline.hip) ----------------------------------------------------------------------
+ * frl/training/representation/step.py:920-928.  z_k [N][K] float32 (the rank-K projection of the type embeddings, 1 <= K <= 64),
+ * spec [N][T][C] float32 (T >= 1, 1 <= C <= 256, T * C < 2^31), N >= 2, 1 <= k <= min(64, N - 1).  Per anchor i: sim(i, j) =
+ * sum_c z_k[i][c] z_k[j][c] in float32 (a NaN ranks as -inf); idx [N][k] int64 = the k rows j != i of largest sim in (sim descending,
+ * index ascending) order; s_hat [N][C] = (sum over those rows, in rank order, of mean_t spec[j][t][c]) / k; out [N][T][C] =
+ * spec - s_hat.  No [N][N] array is formed, no float atomics: bit-reproducible.  Workspace: frl_type_baseline_workspace_bytes(N, C)
+ * (the time means). */
+size_t frl_type_baseline_workspace_bytes(int N, int C);
+int frl_type_baseline(const float* z_k, const float* spec, int N, int K, int T, int C, int k, float* out, float* s_hat, int64_t* idx, void* ws,
+                      size_t ws_bytes, frl_stream_t stream);
+
+/* ---- phase-type leakage loss (csrc/leakage.hip) -----------------------------------------------------------------------------------
+ * frl/training/representation/step.py:1015-1021 over rows h [N][P] and z [N][Dz] (dtypes 0 = float32, 1 = bfloat16, independently;
+ * N >= 1, 1 <= P <= 64, 1 <= Dz <= 128; f32 statistics): C = h_c^T z_c / max(N-1, 1) with the moments taken about a pivot (the mean of
+ * the first min(N, 64) rows), stats [2] = (loss = sqrt(sum C^2), 1 / (max(N-1, 1) loss) or 0 where loss == 0).  cmat [P][Dz] = C and
+ * centre [2][Dz] = pivot_z | mean_z - pivot_z are written when both are non-NULL and are what frl_leakage_bwd reads:
+ * dh[n][p] = g[0] stats[1] sum_d z_c[n][d] C[p][d], in h_dtype; exactly zero where loss == 0 (the reference gives NaN there).
+ * No float atomics: both calls are bit-reproducible.  Workspace: frl_leakage_workspace_bytes(N, P, Dz). */
+size_t frl_leakage_workspace_bytes(int64_t N, int P, int Dz);
+int frl_leakage_fwd(const void* h, int h_dtype, const void* z, int z_dtype, int64_t N, int P, int Dz, float* stats, float* cmat, float* centre,
+                    void* ws, size_t ws_bytes, frl_stream_t stream);
+int frl_leakage_bwd(const void* z, int z_dtype, const float* cmat, const float* centre, const float* stats, const float* g, int64_t N, int P,
+                    int Dz, void* dh, int h_dtype, frl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,11 @@ SIGNATURES = {
     "frl_mutual_knn": (c_int, [P, I, I, P, P, F, I, P, P, P]),
     "frl_phase_pairs_max_points": (S, [I]),
     "frl_phase_pairs": (c_int, [P, P, I, I, I, P, P, I, I, I, I, F] + [P] * 11),
+    "frl_type_baseline_workspace_bytes": (S, [I, I]),
+    "frl_type_baseline": (c_int, [P, P, I, I, I, I, I, P, P, P, P, S, P]),
+    "frl_leakage_workspace_bytes": (S, [L, I, I]),
+    "frl_leakage_fwd": (c_int, [P, I, P, I, L, I, I, P, P, P, P, S, P]),
+    "frl_leakage_bwd": (c_int, [P, I, P, P, P, P, L, I, I, P, I, P]),
     "frl_host_parallel_copy": (c_int, [P, P, S, I]),
     "frl_normalize_chunk_tiles": (c_int, [P, I, I, I, I, I, P, I, I, P, P, I, P, P]),
     "frl_conv3x3_fwd": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P, S, P]),

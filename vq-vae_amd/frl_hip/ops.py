@@ -1463,6 +1463,118 @@ def vicreg_bwd(x: torch.Tensor, cov: torch.Tensor, centre: torch.Tensor, g3: tor
 
 
 # ----------------------------------------------------------------------------------------------
+# type-local spectral baseline (csrc/type_baseline.hip)
+# ----------------------------------------------------------------------------------------------
+TYPE_BASELINE_MAX_K, TYPE_BASELINE_MAX_NBRS, TYPE_BASELINE_MAX_C = 64, 64, 256
+
+
+def chk_type_baseline(z_k: torch.Tensor, spec: torch.Tensor, k_nbrs: int) -> int:
+    """Every limit of frl_type_baseline that needs no device (ValueError); -> k = min(k_nbrs, N - 1)."""
+    if z_k.dim() != 2 or spec.dim() != 3:
+        raise ValueError(f"type_baseline: expected z_k [N, K] and spec [N, T, C], got {tuple(z_k.shape)} and {tuple(spec.shape)}")
+    if z_k.shape[0] != spec.shape[0]:
+        raise ValueError(f"type_baseline: z_k has {z_k.shape[0]} rows and spec {spec.shape[0]}")
+    n, kw = z_k.shape
+    t, c = spec.shape[1], spec.shape[2]
+    if n < 2:
+        raise ValueError("type_baseline: needs N >= 2 anchors (an anchor is never its own neighbour; the reference gives NaN at N = 1)")
+    if not 1 <= kw <= TYPE_BASELINE_MAX_K:
+        raise ValueError(f"type_baseline: the projected width K must be in 1..{TYPE_BASELINE_MAX_K}, got {kw}")
+    if not 1 <= int(k_nbrs) <= TYPE_BASELINE_MAX_NBRS:
+        raise ValueError(f"type_baseline: k_nbrs must be in 1..{TYPE_BASELINE_MAX_NBRS} (one lane per neighbour), got {k_nbrs}")
+    if not 1 <= c <= TYPE_BASELINE_MAX_C:
+        raise ValueError(f"type_baseline: 1 <= C <= {TYPE_BASELINE_MAX_C} spectral channels, got {c}")
+    if t < 1 or t * c >= 2 ** 31 or n * max(kw, c) >= 2 ** 31:
+        raise ValueError(f"type_baseline: T must be positive and T * C, N * K and N * C below 2^31, got {tuple(spec.shape)}")
+    for x, name in ((z_k, "z_k"), (spec, "spec")):
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError(f"type_baseline: {name} must be a contiguous float32 tensor, got {x.dtype} stride {x.stride()}")
+    return min(int(k_nbrs), n - 1)
+
+
+@_timed("type_baseline")
+def type_baseline(z_k: torch.Tensor, spec: torch.Tensor, k_nbrs: int = 20):
+    """z_k [N, K] float32, spec [N, T, C] float32 -> (spec - s_hat [N, T, C] float32, s_hat [N, C] float32, topk_idx [N, k] int64),
+    k = min(k_nbrs, N - 1).  include/frl_hip.h (frl_type_baseline) has the definitions.  No host read."""
+    k = chk_type_baseline(z_k, spec, k_nbrs)
+    if not z_k.is_cuda or not spec.is_cuda:
+        raise _lib.FrlHipError("type_baseline: tensors must live on the GPU (no CPU fallback)")
+    if z_k.device != spec.device:
+        raise ValueError("type_baseline: z_k and spec must be on one device")
+    n, kw = z_k.shape
+    t, c = spec.shape[1], spec.shape[2]
+    out = torch.empty_like(spec)
+    s_hat = torch.empty((n, c), dtype=torch.float32, device=spec.device)
+    idx = torch.empty((n, k), dtype=torch.int64, device=spec.device)
+    lib = _lib.load()
+    ws = workspace(lib.frl_type_baseline_workspace_bytes(n, c), spec.device)
+    check(lib.frl_type_baseline(_p(z_k), _p(spec), n, kw, t, c, k, _p(out), _p(s_hat), _p(idx), _p(ws), ws.numel(), _stream()),
+          "frl_type_baseline")
+    return out, s_hat, idx
+
+
+# ----------------------------------------------------------------------------------------------
+# phase-type leakage loss (csrc/leakage.hip)
+# ----------------------------------------------------------------------------------------------
+LEAKAGE_MAX_P, LEAKAGE_MAX_DZ = 64, 128
+
+
+def chk_leakage(h: torch.Tensor, z: torch.Tensor, name: str = "leakage"):
+    """Every limit of frl_leakage_fwd that needs no device (ValueError)."""
+    if h.dim() != 2 or z.dim() != 2 or h.shape[0] != z.shape[0] or h.shape[0] < 1:
+        raise ValueError(f"{name}: expected h [N, P] and z [N, Dz] with N >= 1, got {tuple(h.shape)} and {tuple(z.shape)}")
+    if not 1 <= h.shape[1] <= LEAKAGE_MAX_P:
+        raise ValueError(f"{name}: supports 1 <= P <= {LEAKAGE_MAX_P} columns of h, got {h.shape[1]}")
+    if not 1 <= z.shape[1] <= LEAKAGE_MAX_DZ:
+        raise ValueError(f"{name}: supports 1 <= Dz <= {LEAKAGE_MAX_DZ} columns of z, got {z.shape[1]}")
+    for x, what in ((h, "h"), (z, "z")):
+        if x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous float32 or bfloat16 tensor, got {x.dtype} stride {x.stride()}")
+
+
+def _chk_leakage_dev(h_like: torch.Tensor, z: torch.Tensor, name: str):
+    if not h_like.is_cuda or not z.is_cuda:
+        raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+    if h_like.device != z.device:
+        raise ValueError(f"{name}: h and z must be on one device")
+
+
+@_timed("leakage_fwd")
+def leakage_fwd(h: torch.Tensor, z: torch.Tensor, want_grad: bool = True):
+    """h [N, P], z [N, Dz] (float32 | bfloat16 each) -> (stats f32 [2] = loss, 1 / (max(N-1, 1) loss) or 0; cmat f32 [P, Dz] = the
+    cross-covariance; centre f32 [2, Dz] = the pivot of z | mean - pivot); cmat and centre (what leakage_bwd reads) are None unless
+    want_grad."""
+    chk_leakage(h, z, "leakage_fwd")
+    _chk_leakage_dev(h, z, "leakage_fwd")
+    n, p = h.shape
+    dz = z.shape[1]
+    stats = torch.empty(2, dtype=torch.float32, device=h.device)
+    cmat = torch.empty(p, dz, dtype=torch.float32, device=h.device) if want_grad else None
+    centre = torch.empty(2, dz, dtype=torch.float32, device=h.device) if want_grad else None
+    lib = _lib.load()
+    ws = workspace(lib.frl_leakage_workspace_bytes(n, p, dz), h.device)
+    check(lib.frl_leakage_fwd(_p(h), _dt(h), _p(z), _dt(z), n, p, dz, _p(stats), _p(cmat), _p(centre), _p(ws), ws.numel(), _stream()),
+          "frl_leakage_fwd")
+    return stats, cmat, centre
+
+
+@_timed("leakage_bwd")
+def leakage_bwd(z: torch.Tensor, cmat: torch.Tensor, centre: torch.Tensor, stats: torch.Tensor, g: torch.Tensor, p: int,
+                dtype: torch.dtype) -> torch.Tensor:
+    """dh [N, p] in `dtype` for the upstream gradient g f32 [1], read on the device; zeros where the loss is zero."""
+    n, dz = z.shape
+    dh = torch.empty((n, p), dtype=dtype, device=z.device)
+    chk_leakage(dh, z, "leakage_bwd")
+    _chk_leakage_dev(dh, z, "leakage_bwd")
+    for t, shape, name in ((cmat, (p, dz), "cmat"), (centre, (2, dz), "centre"), (stats, (2,), "stats"), (g, (1,), "g")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != z.device:
+            raise ValueError(f"leakage_bwd: {name} must be a contiguous float32 {shape} tensor on the device of z")
+    check(_lib.load().frl_leakage_bwd(_p(z), _dt(z), _p(cmat), _p(centre), _p(stats), _p(g), n, p, dz, _p(dh), _dt(dh), _stream()),
+          "frl_leakage_bwd")
+    return dh
+
+
+# ----------------------------------------------------------------------------------------------
 # soft-neighbourhood matching loss (csrc/soft_neighborhood.hip)
 # ----------------------------------------------------------------------------------------------
 SOFT_NBR_MAX_M, SOFT_NBR_MAX_WIDTH = 32, 256
