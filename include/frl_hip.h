@@ -71,6 +71,10 @@ int frl_conv1x1_bwd_data_add(const void* dy, const void* y, int act, const float
 /* Tuning hook (no reference counterpart): upper bound of the workgroups, i.e. float32 partial slabs, of a 1x1 weight-gradient launch;
  * returns the previous bound.  frl_conv1x1_bwd_weight_workspace_bytes follows it: size workspaces after changing it. */
 int frl_wgrad_set_max_workgroups(int n);
+/* A/B hook: 1 (default) = bf16 weight gradients with Cin = 64, Cout in {4, 8, 12, 16}, no mask, no time shift, whole 64-row tiles and
+ * 16-byte aligned operands (the 64 -> 12 phase head) take the streaming kernel pw_wgrad_thin_kernel, 0 = every call takes the generic
+ * kernel; same workgroups, slabs and bits either way.  Returns the previous setting. */
+int frl_wgrad_thin(int on);
 size_t frl_conv1x1_bwd_weight_workspace_bytes(int64_t P, int Cin, int Cout);
 int frl_conv1x1_bwd_weight(const void* dy, const void* y, int act, const void* x, float* dw, float* dbias, int64_t P,
                            int Cin, int Cout, int dtype, void* ws, size_t ws_bytes, frl_stream_t stream);

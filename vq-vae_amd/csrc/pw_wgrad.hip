@@ -289,6 +289,11 @@ static int dispatch_wgrad(const void* dy, const void* ymask, int mask_act, const
   return frl_fail(-2, "conv1x1_bwd_weight: unsupported (Cout, Cin) combination");
 }
 
+// streaming kernel for thin bf16 outputs (pw_wgrad_thin.hip)
+bool pwt_supported(const void* dy, const void* ymask, const void* x, int64_t P, int Cin, int Cout, int64_t ldy, int T, int toff, int dtype,
+                   int flags);
+int pwt_launch(const void* dy, const void* x, float* ws, int64_t P, int Cout, int nwg, int64_t rows, hipStream_t st);
+
 extern "C" {
 
 // Tuning hook: upper bound of the workgroups (= float32 slabs to reduce) a weight-gradient launch uses; returns the previous bound.
@@ -324,7 +329,12 @@ static int conv_tap_bwd_weight(const void* dy, const void* y, int act, const voi
     const char* dyp = (const char*)dy + (size_t)oc0 * esz;
     const char* ymp = ym ? (const char*)ym + (size_t)oc0 * esz : nullptr;
     int rc;
-    if (dtype == FRL_F32) rc = dispatch_wgrad<float>(dyp, ymp, act, x, (float*)ws, P, co, Cin, HW, T, toff, 0, Cout, stream);
+    if (pwt_supported(dyp, ymp, x, P, Cin, co, Cout, T, toff, dtype, flags)) {
+      // thin bf16 outputs (the 64 -> 12 phase head): streaming kernel, same workgroups, row ranges, slabs and bits as launch_wgrad's
+      const int nwg = wgrad_nwg(P);
+      const int64_t rows = ((P + nwg - 1) / nwg + WG_KP - 1) / WG_KP * WG_KP;
+      rc = pwt_launch(dyp, x, (float*)ws, P, co, nwg, rows, stream);
+    } else if (dtype == FRL_F32) rc = dispatch_wgrad<float>(dyp, ymp, act, x, (float*)ws, P, co, Cin, HW, T, toff, 0, Cout, stream);
     else if (dtype == FRL_BF16) rc = dispatch_wgrad<bf16>(dyp, ymp, act, x, (float*)ws, P, co, Cin, HW, T, toff, use_tr, Cout, stream);
     else return frl_fail(-2, "bwd_weight: bad dtype");
     if (rc) return rc;

@@ -352,6 +352,12 @@ def _conv1x1_bwd_weight_impl(dy: torch.Tensor, x: torch.Tensor, y: Optional[torc
 conv1x1_bwd_weight = _timed("conv1x1_bwd_weight")(_conv1x1_bwd_weight_impl)
 
 
+def wgrad_thin(on: bool) -> bool:
+    """A/B hook (include/frl_hip.h: frl_wgrad_thin): True (default) = eligible thin-output bf16 weight gradients (the 64 -> 12 phase head)
+    take the streaming kernel, False = every call takes the generic kernel; same bits.  Returns the previous setting."""
+    return bool(_lib.load().frl_wgrad_thin(1 if on else 0))
+
+
 # ----------------------------------------------------------------------------------------------
 # vector quantizer (csrc/vq.hip)
 # ----------------------------------------------------------------------------------------------
