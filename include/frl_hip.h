@@ -604,7 +604,45 @@ int frl_phase_pairs(const float* spec, const float* ysfc, int N, int D, int T, c
                     uint8_t* keep_overlap, float* weight, float* dist, uint8_t* anchor_ok, int32_t* counters, int32_t* flag,
                     frl_stream_t stream);
 
-/* ---- type-local spectral baseline (csrc/type_baseline.hip) ----------------------------------------------------------------------
+/* ---- spatial InfoNCE pair mining (csrc/spatial_pairs.hip) -------------------------------------------------------------------------
+ * frl/training/representation/step.py:323-401 with frl/utils/spatial.py:176-332 (spatial_knn_pairs, spatial_negative_pairs) for every
+ * segment (sample) of a batch per launch.  masks [S][H][W] bool bytes, anchors [N][2] int32 (row, col) concatenated over the samples,
+ * seg_host / seg: the S + 1 offsets rising from 0 to N on the host (checked, sizes the grid) and on the device; segments may be empty.
+ * 1 <= S <= 4096, 1 <= H, W <= frl_spatial_pairs_max_hw() (1024), 1 <= N <= 2^24; anything else returns a negative code before a launch.
+ * An anchor outside [0, H) x [0, W) ORs 1 into *flag, reads nothing and gets no neighbour, no negative and no index.
+ * counters [S] are ADDED to and *flag is OR-ed: the caller zeroes both.
+ * frl_spatial_pack_mask: bits [S][H][ceil(W / 32)] 32-bit words, bit c % 32 of word c / 32 = pixel (r, c); the bits beyond W are 0.
+ * frl_spatial_knn: offsets [k][2] int32 (dr, dc) on the device, 1 <= k <= 64 -> pos_rc [N][k][2] = anchor + offset, pos_valid [N][k] = 1
+ *   iff that pixel is inside the grid and its bit is set; counters[s] += valid slots of segment s.
+ * frl_spatial_negatives: the candidates of anchor (r, c) are the set pixels (y, x) of its segment's mask with
+ *   lo <= (y - r)^2 + (x - c)^2 <= hi, in row-major order (lo > hi: none; hi is capped at (H - 1)^2 + (W - 1)^2); cnt is their number
+ *   (popcounts of mask rows under at most two column intervals per row, integer square roots only).  draws [N][n_per_anchor] int32 in
+ *   [0, 2^31), 1 <= n_per_anchor <= 64; a negative draw ORs 2 into *flag and is taken without its sign bit.  With m = min(n_per_anchor, cnt)
+ *   draw j < m has the rank q = (uint64(draw) * (cnt - j)) >> 31 among the remaining candidates; going through the earlier picks in
+ *   ascending order, q += 1 while q >= the pick, gives its rank among all candidates: uniform without replacement.
+ *   neg_rc [N][n_per_anchor][2] holds the picks in draw order (-1 beyond m), neg_count [N] = m, counters[s] += the m of segment s.
+ * frl_spatial_pair_index: per segment the sorted unique list of the anchors, the valid neighbours and the negatives (what
+ *   torch.unique(dim=0) returns: ascending r * W + c), as set bits of a bitmap of H * W bits; the index of a coordinate is the number of
+ *   set bits below its key.  unique_seg [S + 1] = offsets of the segments in unique_rc [N * (1 + k + n_per_anchor)][2] (capacity; the
+ *   first unique_seg[S] rows are written); anchor_idx [N], pos_idx [N][k], neg_idx [N][n_per_anchor] = rows of unique_rc (shifted by the
+ *   segment's offset), -1 for a slot that holds nothing.  feat [S][C][H][W] float32 (1 <= C <= 256, tau > 0):
+ *   per pair slot d = sqrtf(sum_c (f_anchor - f_other)^2) in float32, channels ascending; pos_w = clamp(expf(-d / tau), min_w, 1),
+ *   neg_w = clamp(1 - expf(-d / tau), min_w, 1); 0 for a slot that holds nothing.  Workspaces: bitmap S * ceil(H * W / 32) words
+ *   (zeroed by the call), wordpre S * (ceil(H * W / 32) + 1) int32. */
+int frl_spatial_pairs_max_hw(void);
+int frl_spatial_pack_mask(const uint8_t* mask, int S, int H, int W, uint32_t* bits, frl_stream_t stream);
+int frl_spatial_knn(const uint32_t* bits, int S, int H, int W, const int32_t* anchors, int N, const int32_t* seg_host, const int32_t* seg,
+                    const int32_t* offsets, int k, int32_t* pos_rc, uint8_t* pos_valid, int32_t* counters, int32_t* flag, frl_stream_t stream);
+int frl_spatial_negatives(const uint32_t* bits, int S, int H, int W, const int32_t* anchors, int N, const int32_t* seg_host, const int32_t* seg,
+                          int lo, int hi, int n_per_anchor, const int32_t* draws, int32_t* neg_rc, int32_t* neg_count, int32_t* counters,
+                          int32_t* flag, frl_stream_t stream);
+int frl_spatial_pair_index(int S, int H, int W, const int32_t* anchors, int N, const int32_t* seg_host, const int32_t* seg, const int32_t* pos_rc,
+                           const uint8_t* pos_valid, int k, const int32_t* neg_rc, const int32_t* neg_count, int n_per_anchor, const float* feat,
+                           int C, float tau, float min_w, uint32_t* bitmap, int32_t* wordpre, int32_t* unique_seg, int32_t* unique_rc,
+                           int32_t* anchor_idx, int32_t* pos_idx, int32_t* neg_idx, float* pos_w, float* pos_d, float* neg_w, float* neg_d,
+                           frl_stream_t stream);
+
+/* ---- type-local spectral baseline (csrc/type_baseline.hip)----------------------------------------------------------------------
  * frl/training/representation/step.py:920-928.  z_k [N][K] float32 (the rank-K projection of the type embeddings, 1 <= K <= 64),
  * spec [N][T][C] float32 (T >= 1, 1 <= C <= 256, T * C < 2^31), N >= 2, 1 <= k <= min(64, N - 1).  Per anchor i: sim(i, j) =
  * sum_c z_k[i][c] z_k[j][c] in float32 (a NaN ranks as -inf); idx [N][k] int64 = the k rows j != i of largest sim in (sim descending,

@@ -99,6 +99,11 @@ SIGNATURES = {
     "frl_mutual_knn": (c_int, [P, I, I, P, P, F, I, P, P, P]),
     "frl_phase_pairs_max_points": (S, [I]),
     "frl_phase_pairs": (c_int, [P, P, I, I, I, P, P, I, I, I, I, F] + [P] * 11),
+    "frl_spatial_pairs_max_hw": (c_int, []),
+    "frl_spatial_pack_mask": (c_int, [P, I, I, I, P, P]),
+    "frl_spatial_knn": (c_int, [P, I, I, I, P, I, P, P, P, I, P, P, P, P, P]),
+    "frl_spatial_negatives": (c_int, [P, I, I, I, P, I, P, P, I, I, I, P, P, P, P, P, P]),
+    "frl_spatial_pair_index": (c_int, [I, I, I, P, I, P, P, P, P, I, P, P, I, P, I, F, F] + [P] * 12),
     "frl_type_baseline_workspace_bytes": (S, [I, I]),
     "frl_type_baseline": (c_int, [P, P, I, I, I, I, I, P, P, P, P, S, P]),
     "frl_leakage_workspace_bytes": (S, [L, I, I]),

@@ -7,5 +7,6 @@ from .evt_soft_neighborhood import EvtDiffusionMetric, evt_soft_neighborhood_los
 from .phase_margin import (phase_recovery_discrimination_loss, compute_phase_spread_ranking, phase_spread_ranking_gathered,  # noqa: F401
                            phase_spread_ranking_loss)
 from .phase_pairs import build_phase_pairs, build_phase_pairs_batched  # noqa: F401
+from .spatial_pairs import build_spatial_pairs, build_spatial_pairs_batched  # noqa: F401
 from .type_baseline import type_local_baseline, type_projection  # noqa: F401
 from .leakage import phase_type_leakage_loss  # noqa: F401

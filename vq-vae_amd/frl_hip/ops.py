@@ -816,6 +816,107 @@ def phase_pairs(spec: torch.Tensor, ysfc: torch.Tensor, seg: torch.Tensor, seg_h
     return out
 
 
+def _at(t: torch.Tensor, element: int):
+    return ctypes.c_void_p(t.data_ptr() + element * t.element_size())
+
+
+def _chk_spatial(bits, anchors, seg, seg_host, what):
+    if not bits.is_cuda or not anchors.is_cuda:
+        raise _lib.FrlHipError(f"{what}: tensors must live on the GPU (no CPU fallback)")
+    if bits.dtype != torch.int32 or bits.dim() != 3 or not bits.is_contiguous():
+        raise ValueError(f"{what}: the packed masks must be a contiguous int32 [S, H, ceil(W / 32)] tensor (spatial_pack_mask)")
+    if anchors.dtype != torch.int32 or anchors.dim() != 2 or anchors.shape[1] != 2 or anchors.shape[0] == 0 or not anchors.is_contiguous():
+        raise ValueError(f"{what}: anchors must be a contiguous int32 [N, 2] tensor with N > 0, got {tuple(anchors.shape)} {anchors.dtype}")
+    if seg_host.is_cuda or seg_host.dtype != torch.int32 or seg_host.shape != (bits.shape[0] + 1,) or not seg_host.is_contiguous():
+        raise ValueError(f"{what}: the host segment offsets must be a contiguous int32 [{bits.shape[0] + 1}] CPU tensor")
+    if seg.dtype != torch.int32 or seg.shape != seg_host.shape or not seg.is_contiguous() or seg.device != anchors.device:
+        raise ValueError(f"{what}: the device segment offsets must be a contiguous int32 [{seg_host.numel()}] tensor on the device of anchors")
+
+
+@_timed("spatial_pack_mask")
+def spatial_pack_mask(masks: torch.Tensor) -> torch.Tensor:
+    """masks [S, H, W] bool -> int32 [S, H, ceil(W / 32)]: bit c % 32 of word c / 32 is pixel (r, c).  No host read."""
+    if masks.dim() != 3 or masks.dtype != torch.bool or 0 in masks.shape:
+        raise ValueError(f"spatial_pack_mask: expected a bool [S, H, W] tensor, got {tuple(masks.shape)} {masks.dtype}")
+    if not masks.is_cuda:
+        raise _lib.FrlHipError("spatial_pack_mask: tensors must live on the GPU (no CPU fallback)")
+    masks = masks.contiguous()
+    s, h, w = masks.shape
+    bits = torch.empty((s, h, (w + 31) // 32), dtype=torch.int32, device=masks.device)
+    check(_lib.load().frl_spatial_pack_mask(_p(masks), s, h, w, _p(bits), _stream()), "frl_spatial_pack_mask")
+    return bits
+
+
+@_timed("spatial_knn")
+def spatial_knn(bits: torch.Tensor, w: int, anchors: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor, offsets: torch.Tensor,
+                meta: torch.Tensor, counters_at: int, flag_at: int):
+    """bits from spatial_pack_mask of masks [S, H, w], anchors int32 [N, 2], offsets int32 [k, 2] on the device -> (pos_rc int32 [N, k, 2],
+    pos_valid uint8 [N, k]); meta[counters_at : counters_at + S] += valid slots per segment, meta[flag_at] |= 1 for an anchor outside the
+    grid.  include/frl_hip.h (frl_spatial_knn) has the definitions.  No host read."""
+    _chk_spatial(bits, anchors, seg, seg_host, "spatial_knn")
+    k, n, dev = offsets.shape[0], anchors.shape[0], anchors.device
+    if offsets.dtype != torch.int32 or offsets.dim() != 2 or offsets.shape[1] != 2 or not 1 <= k <= 64 or not offsets.is_contiguous() \
+            or offsets.device != dev:
+        raise ValueError("spatial_knn: offsets must be a contiguous int32 [k, 2] tensor on the device of anchors, 1 <= k <= 64")
+    pos_rc = torch.empty((n, k, 2), dtype=torch.int32, device=dev)
+    pos_valid = torch.empty((n, k), dtype=torch.uint8, device=dev)
+    check(_lib.load().frl_spatial_knn(_p(bits), bits.shape[0], bits.shape[1], int(w), _p(anchors), n, _p(seg_host), _p(seg), _p(offsets), k,
+                                      _p(pos_rc), _p(pos_valid), _at(meta, counters_at), _at(meta, flag_at), _stream()), "frl_spatial_knn")
+    return pos_rc, pos_valid
+
+
+@_timed("spatial_negatives")
+def spatial_negatives(bits: torch.Tensor, w: int, anchors: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor, lo: int, hi: int,
+                      draws: torch.Tensor, meta: torch.Tensor, counters_at: int, flag_at: int):
+    """draws int32 [N, n_per_anchor] in [0, 2^31) -> (neg_rc int32 [N, n_per_anchor, 2], neg_count int32 [N]); lo / hi: the integer bounds on
+    the squared distance.  meta[counters_at : counters_at + S] += negatives per segment, meta[flag_at] |= 1 for an anchor outside the grid,
+    |= 2 for a negative draw.  include/frl_hip.h (frl_spatial_negatives) has the definitions.  No host read."""
+    _chk_spatial(bits, anchors, seg, seg_host, "spatial_negatives")
+    n, dev = anchors.shape[0], anchors.device
+    if draws.dtype != torch.int32 or draws.dim() != 2 or draws.shape[0] != n or not 1 <= draws.shape[1] <= 64 or not draws.is_contiguous() \
+            or draws.device != dev:
+        raise ValueError(f"spatial_negatives: draws must be a contiguous int32 [{n}, n_per_anchor] tensor on the device of anchors, "
+                         "1 <= n_per_anchor <= 64")
+    n_per = draws.shape[1]
+    neg_rc = torch.empty((n, n_per, 2), dtype=torch.int32, device=dev)
+    neg_count = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.load().frl_spatial_negatives(_p(bits), bits.shape[0], bits.shape[1], int(w), _p(anchors), n, _p(seg_host), _p(seg), int(lo),
+                                            int(hi), n_per, _p(draws), _p(neg_rc), _p(neg_count), _at(meta, counters_at), _at(meta, flag_at),
+                                            _stream()), "frl_spatial_negatives")
+    return neg_rc, neg_count
+
+
+@_timed("spatial_pair_index")
+def spatial_pair_index(h: int, w: int, anchors: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor, pos_rc: torch.Tensor,
+                       pos_valid: torch.Tensor, neg_rc: torch.Tensor, neg_count: torch.Tensor, feat: torch.Tensor, tau: float, min_w: float,
+                       meta: torch.Tensor, unique_seg_at: int):
+    """The outputs of spatial_knn and spatial_negatives and feat float32 [S, C, H, W] -> dict of unique_rc int32 [N (1 + k + n), 2] (the
+    first meta[unique_seg_at + S] rows are written), anchor_idx [N], pos_idx [N, k], neg_idx [N, n] int32 (-1: the slot holds nothing),
+    pos_w / pos_d [N, k], neg_w / neg_d [N, n] float32; meta[unique_seg_at : unique_seg_at + S + 1] = the segments' offsets in unique_rc.
+    include/frl_hip.h (frl_spatial_pair_index) has the definitions.  No host read."""
+    n, dev, s = anchors.shape[0], anchors.device, seg_host.numel() - 1
+    k, n_per = pos_valid.shape[1], neg_rc.shape[1]
+    if feat.dtype != torch.float32 or feat.dim() != 4 or feat.shape[0] != s or tuple(feat.shape[2:]) != (h, w) or not feat.is_contiguous() \
+            or not 1 <= feat.shape[1] <= 256 or feat.device != dev:
+        raise ValueError(f"spatial_pair_index: feat must be a contiguous float32 [{s}, C <= 256, {h}, {w}] tensor on the device of anchors")
+    if not float(tau) > 0.0:
+        raise ValueError(f"spatial_pair_index: tau must be positive, got {tau}")
+    nwb = (h * w + 31) // 32
+    bitmap = torch.empty(s * nwb, dtype=torch.int32, device=dev)
+    wordpre = torch.empty(s * (nwb + 1), dtype=torch.int32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"unique_rc": torch.empty((n * (1 + k + n_per), 2), **i32), "anchor_idx": torch.empty(n, **i32), "pos_idx": torch.empty((n, k), **i32),
+           "neg_idx": torch.empty((n, n_per), **i32), "pos_w": torch.empty((n, k), **f32), "pos_d": torch.empty((n, k), **f32),
+           "neg_w": torch.empty((n, n_per), **f32), "neg_d": torch.empty((n, n_per), **f32)}
+    check(_lib.load().frl_spatial_pair_index(s, int(h), int(w), _p(anchors), n, _p(seg_host), _p(seg), _p(pos_rc), _p(pos_valid), k, _p(neg_rc),
+                                             _p(neg_count), n_per, _p(feat), feat.shape[1], float(tau), float(min_w), _p(bitmap), _p(wordpre),
+                                             _at(meta, unique_seg_at), _p(out["unique_rc"]), _p(out["anchor_idx"]), _p(out["pos_idx"]),
+                                             _p(out["neg_idx"]), _p(out["pos_w"]), _p(out["pos_d"]), _p(out["neg_w"]), _p(out["neg_d"]),
+                                             _stream()), "frl_spatial_pair_index")
+    return out
+
+
 @_timed("normalize_tiles")
 def normalize_tiles(raw: torch.Tensor, table: torch.Tensor, valid: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16,
                     out: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
