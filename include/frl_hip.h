@@ -642,6 +642,38 @@ int frl_spatial_pair_index(int S, int H, int W, const int32_t* anchors, int N, c
                            int32_t* anchor_idx, int32_t* pos_idx, int32_t* neg_idx, float* pos_w, float* pos_d, float* neg_w, float* neg_d,
                            frl_stream_t stream);
 
+/* ---- anchor sampling (csrc/anchors.hip) -------------------------------------------------------------------------------------------
+ * frl/data/sampling/anchor_sampling.py for S samples per launch, one workgroup per sample.  bits: the packed masks of
+ * frl_spatial_pack_mask.  1 <= S <= 4096, 1 <= H, W <= frl_spatial_pairs_max_hw(); anything outside the stated limits returns a negative
+ * code before a launch.  *flag is OR-ed (the caller zeroes it): 1 a jitter outside [-jitter_radius, jitter_radius], 2 a non-finite weight
+ * at a masked pixel, 4 a negative or NaN noise at a masked pixel, 8 more than 4096 distinct values.
+ * frl_anchor_grid_max: the largest number of grid points of a sample over all allowed jitters (the jitter -jitter_radius on both axes);
+ *   stride >= 1, 0 <= jitter_radius <= border <= 1024, at most 16384 points.
+ * frl_anchor_grid (sample_anchors_grid, :69-113): jitter [S][2] int32 (row, col) on the device.  The grid points of sample s are
+ *   (border + jr + i stride, border + jc + j stride) for all rows < H - border and cols < W - border; those whose mask bit is set are
+ *   written in row-major order to grid_rc [S][gmax][2] (gmax >= frl_anchor_grid_max; -1 beyond the count), their number to counts [S].
+ *   A sample whose jitter is out of range gets no point and raises flag 1.
+ * frl_anchor_supplement (:150-178): weights [S][H][W] float32 or NULL, noise [S][H][W] float32 >= 0 (Exp(1) variates), 0 <= supplement_n
+ *   <= 1024.  A pixel is eligible when its mask bit is set and, with weights, w > 0; a sample with weights but no eligible pixel falls
+ *   back to every masked pixel and ignores the weights.  The key of an eligible pixel is noise (no weights, or the fallback), otherwise
+ *   noise / w rounded to nearest in float32; its sign bit is dropped.  The m = min(supplement_n, eligible) eligible pixels with the smallest
+ *   (key, row * W + col) are written in ascending order of that pair to sup_rc [S][supplement_n][2] (-1 beyond m); counts [S] = m,
+ *   n_valid [S] = set mask bits.  With iid Exp(1) noise this is sampling without replacement, uniform or proportional to the weights
+ *   (the law of torch.multinomial(replacement=False)), in random order.  keys [S][H][W] 32-bit words is a workspace (the key patterns).
+ *   supplement_n = 0: noise, keys and sup_rc may be NULL.
+ * frl_anchor_inverse_frequency (_apply_inverse_frequency, :235-281): data [S][H][W] float32, valid_values a sorted int32 list on the device
+ *   (0 <= n_values <= 4096) or NULL for no list.  A pixel is eligible when its bit is set, data is finite and, with a list,
+ *   (int32) rintf(data) is in it (a rounded value beyond int32 is not).  out [S][H][W] = 1.0f / (float) count for an eligible pixel, count
+ *   = the eligible pixels of the sample whose value compares equal (-0.0 and 0.0 are one value), 0 elsewhere; a sample without an eligible
+ *   pixel gets 1.0 at the set bits.  More than 4096 distinct values in a sample raises flag 8 (the output is then not to be used). */
+int frl_anchor_grid_max(int H, int W, int stride, int border, int jitter_radius);
+int frl_anchor_grid(const uint32_t* bits, int S, int H, int W, int stride, int border, int jitter_radius, const int32_t* jitter, int gmax,
+                    int32_t* grid_rc, int32_t* counts, int32_t* flag, frl_stream_t stream);
+int frl_anchor_supplement(const uint32_t* bits, int S, int H, int W, const float* weights, const float* noise, int supplement_n,
+                          uint32_t* keys, int32_t* sup_rc, int32_t* counts, int32_t* n_valid, int32_t* flag, frl_stream_t stream);
+int frl_anchor_inverse_frequency(const float* data, const uint32_t* bits, int S, int H, int W, const int32_t* valid_values, int n_values,
+                                 float* out, int32_t* flag, frl_stream_t stream);
+
 /* ---- type-local spectral baseline (csrc/type_baseline.hip)----------------------------------------------------------------------
  * frl/training/representation/step.py:920-928.  z_k [N][K] float32 (the rank-K projection of the type embeddings, 1 <= K <= 64),
  * spec [N][T][C] float32 (T >= 1, 1 <= C <= 256, T * C < 2^31), N >= 2, 1 <= k <= min(64, N - 1).  Per anchor i: sim(i, j) =

@@ -104,6 +104,10 @@ SIGNATURES = {
     "frl_spatial_knn": (c_int, [P, I, I, I, P, I, P, P, P, I, P, P, P, P, P]),
     "frl_spatial_negatives": (c_int, [P, I, I, I, P, I, P, P, I, I, I, P, P, P, P, P, P]),
     "frl_spatial_pair_index": (c_int, [I, I, I, P, I, P, P, P, P, I, P, P, I, P, I, F, F] + [P] * 12),
+    "frl_anchor_grid_max": (c_int, [I, I, I, I, I]),
+    "frl_anchor_grid": (c_int, [P, I, I, I, I, I, I, P, I, P, P, P, P]),
+    "frl_anchor_supplement": (c_int, [P, I, I, I, P, P, I, P, P, P, P, P, P]),
+    "frl_anchor_inverse_frequency": (c_int, [P, P, I, I, I, P, I, P, P, P]),
     "frl_type_baseline_workspace_bytes": (S, [I, I]),
     "frl_type_baseline": (c_int, [P, P, I, I, I, I, I, P, P, P, P, S, P]),
     "frl_leakage_workspace_bytes": (S, [L, I, I]),

@@ -917,6 +917,85 @@ def spatial_pair_index(h: int, w: int, anchors: torch.Tensor, seg: torch.Tensor,
     return out
 
 
+def _chk_anchor_bits(bits: torch.Tensor, w: int, what: str):
+    if not bits.is_cuda:
+        raise _lib.FrlHipError(f"{what}: tensors must live on the GPU (no CPU fallback)")
+    if bits.dtype != torch.int32 or bits.dim() != 3 or not bits.is_contiguous() or bits.shape[2] != (int(w) + 31) // 32:
+        raise ValueError(f"{what}: the packed masks must be a contiguous int32 [S, H, ceil(W / 32)] tensor (spatial_pack_mask)")
+
+
+def _chk_anchor_map(t: torch.Tensor, bits: torch.Tensor, w: int, name: str, what: str):
+    shape = (bits.shape[0], bits.shape[1], int(w))
+    if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != bits.device:
+        raise ValueError(f"{what}: {name} must be a contiguous float32 {list(shape)} tensor on the device of the masks, got "
+                         f"{tuple(t.shape)} {t.dtype}")
+
+
+@_timed("anchor_grid")
+def anchor_grid(bits: torch.Tensor, w: int, stride: int, border: int, jitter_radius: int, jitter: torch.Tensor, gmax: int,
+                meta: torch.Tensor, counts_at: int, flag_at: int) -> torch.Tensor:
+    """bits from spatial_pack_mask of masks [S, H, w], jitter int32 [S, 2] on the device -> grid_rc int32 [S, gmax, 2] (-1 beyond the
+    count); meta[counts_at : counts_at + S] = grid points per sample, meta[flag_at] |= 1 for a jitter out of range.  gmax is at least
+    frl_anchor_grid_max.  include/frl_hip.h (frl_anchor_grid) has the definitions.  No host read."""
+    _chk_anchor_bits(bits, w, "anchor_grid")
+    s, dev = bits.shape[0], bits.device
+    if jitter.dtype != torch.int32 or tuple(jitter.shape) != (s, 2) or not jitter.is_contiguous() or jitter.device != dev:
+        raise ValueError(f"anchor_grid: jitter must be a contiguous int32 [{s}, 2] tensor on the device of the masks")
+    grid_rc = torch.empty((s, int(gmax), 2), dtype=torch.int32, device=dev)
+    check(_lib.load().frl_anchor_grid(_p(bits), s, bits.shape[1], int(w), int(stride), int(border), int(jitter_radius), _p(jitter), int(gmax),
+                                      _p(grid_rc), _at(meta, counts_at), _at(meta, flag_at), _stream()), "frl_anchor_grid")
+    return grid_rc
+
+
+@_timed("anchor_supplement")
+def anchor_supplement(bits: torch.Tensor, w: int, weights: Optional[torch.Tensor], noise: Optional[torch.Tensor], supplement_n: int,
+                      meta: torch.Tensor, counts_at: int, valid_at: int, flag_at: int) -> torch.Tensor:
+    """weights float32 [S, H, w] or None, noise float32 [S, H, w] >= 0 (None only with supplement_n = 0) -> sup_rc int32
+    [S, supplement_n, 2]: the min(supplement_n, eligible) eligible pixels of smallest (noise / weight, pixel index), ascending, -1 beyond;
+    meta[counts_at : + S] = picks per sample, meta[valid_at : + S] = valid pixels per sample, meta[flag_at] |= 2 for a non-finite weight,
+    |= 4 for a negative or NaN noise at a valid pixel.  include/frl_hip.h (frl_anchor_supplement) has the definitions.  No host read."""
+    _chk_anchor_bits(bits, w, "anchor_supplement")
+    n = int(supplement_n)
+    if not 0 <= n <= 1024:
+        raise ValueError(f"anchor_supplement: supplement_n must be in 0..1024, got {supplement_n}")
+    if weights is not None:
+        _chk_anchor_map(weights, bits, w, "weights", "anchor_supplement")
+    if noise is not None:
+        _chk_anchor_map(noise, bits, w, "noise", "anchor_supplement")
+    elif n > 0:
+        raise ValueError("anchor_supplement: noise is required when supplement_n > 0")
+    s = bits.shape[0]
+    sup_rc = torch.empty((s, n, 2), dtype=torch.int32, device=bits.device)
+    keys = torch.empty((s, bits.shape[1], int(w)), dtype=torch.int32, device=bits.device) if n else None     # workspace: the key patterns
+    check(_lib.load().frl_anchor_supplement(_p(bits), s, bits.shape[1], int(w), _p(weights), _p(noise), n, _p(keys), _p(sup_rc) if n else _p(None),
+                                            _at(meta, counts_at), _at(meta, valid_at), _at(meta, flag_at), _stream()), "frl_anchor_supplement")
+    return sup_rc
+
+
+@_timed("anchor_inverse_frequency")
+def anchor_inverse_frequency(data: torch.Tensor, bits: torch.Tensor, valid_values: Optional[torch.Tensor], flag: torch.Tensor) -> torch.Tensor:
+    """data float32 [S, H, W], bits the packed valid masks, valid_values a sorted int32 list on the device (possibly empty) or None ->
+    float32 [S, H, W]: 1 / (eligible pixels of the sample with the same value), 0 at ineligible pixels, 1 at the valid pixels of a sample
+    without an eligible one; flag[0] |= 8 for more than 4096 distinct values.  include/frl_hip.h (frl_anchor_inverse_frequency).  No host read."""
+    if data.dim() != 3:
+        raise ValueError(f"anchor_inverse_frequency: data must be [S, H, W], got {tuple(data.shape)}")
+    _chk_anchor_bits(bits, data.shape[2], "anchor_inverse_frequency")
+    _chk_anchor_map(data, bits, data.shape[2], "data", "anchor_inverse_frequency")
+    n_values = 0
+    if valid_values is not None:
+        if valid_values.dtype != torch.int32 or valid_values.dim() != 1 or valid_values.numel() > 4096 or not valid_values.is_contiguous() \
+                or valid_values.device != data.device:
+            raise ValueError("anchor_inverse_frequency: valid_values must be a contiguous int32 list of at most 4096 entries on the device")
+        n_values = valid_values.numel()
+        if n_values == 0:
+            valid_values = torch.zeros(1, dtype=torch.int32, device=data.device)          # a list that holds nothing is still a list
+    out = torch.empty_like(data)
+    s, h, w = data.shape
+    check(_lib.load().frl_anchor_inverse_frequency(_p(data), _p(bits), s, h, w, _p(valid_values), n_values, _p(out), _p(flag), _stream()),
+          "frl_anchor_inverse_frequency")
+    return out
+
+
 @_timed("normalize_tiles")
 def normalize_tiles(raw: torch.Tensor, table: torch.Tensor, valid: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16,
                     out: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
