@@ -674,6 +674,32 @@ int frl_anchor_supplement(const uint32_t* bits, int S, int H, int W, const float
 int frl_anchor_inverse_frequency(const float* data, const uint32_t* bits, int S, int H, int W, const int32_t* valid_values, int n_values,
                                  float* out, int32_t* flag, frl_stream_t stream);
 
+/* ---- cross-patch spectral negatives and pair similarities (csrc/spectral_negatives.hip) --------------------------------------------
+ * frl_spectral_negatives replaces frl/training/representation/step.py:743-773 (the double loop over ordered patch pairs with two
+ *   torch.randint calls each, the concatenations, the two row gathers, the norm and the weight) by one launch.  spec [N][C] float32,
+ *   1 <= C <= 256; offsets [S + 1] int32 on the device, rising from 0 to N with no empty patch, S >= 2; draws [Q][2] int32 in
+ *   [0, 2^31), Q = n_per * S * (S - 1) < 2^31.  Negative q belongs to block b = q / n_per of the reference's loop order: pi = b / (S - 1),
+ *   r = b % (S - 1), pj = r + (r >= pi).  With count_p = offsets[p + 1] - offsets[p]:
+ *     i = offsets[pi] + ((uint64) draws[q][0] * count_pi >> 31),  j = offsets[pj] + ((uint64) draws[q][1] * count_pj >> 31)
+ *   (uniform over the patch to within count / 2^31, never reaching count).  pairs [Q][2] int64 = (i, j); dist [Q] = sqrtf(sum_c
+ *   (spec[i][c] - spec[j][c])^2) in float32 (lane-strided partial sums over 16 lanes, channels ascending, then a butterfly);
+ *   weights [Q] = clamp(1 - expf(-dist / tau), min_w, 1), tau > 0.  A negative draw is taken as 0 and ORs 1 into *index_flag (may be
+ *   NULL; the word behind ops.index_errors()); patch bounds that are not 0 <= offsets[p] < offsets[p + 1] <= N are clamped to a non-empty
+ *   range inside spec and OR 2: no row outside spec is ever read.  Q = 0 is a no-op.
+ * frl_pair_sims replaces the gathers of step.py:569-574 and :798-807: sims [T] = -sum_d (emb[a_t][d] - emb[b_t][d])^2 / D for pairs [T][2]
+ *   int64 over emb [N][D] float32, 1 <= D <= 256 (same summation order).  A row in [-N, 0) wraps, any other row outside [0, N) is clamped
+ *   and ORs 1 into *index_flag (may be NULL).  stats (may be NULL) receives 4 doubles: T, the mean of sims, their unbiased standard
+ *   deviation (NaN when T < 2, as torch.std) and 0; the sums are kept in double, per-workgroup partials in ws
+ *   (frl_pair_sims_workspace_bytes(T), 8-byte aligned; unused without stats), then one workgroup adds them in index order.  No float
+ *   atomics: sims and stats are bit-reproducible.  T = 0 is a no-op (stats is left untouched).
+ * Argument errors (C or D out of range, S < 2 with Q > 0, Q != n_per * S * (S - 1), tau <= 0, a NULL pointer with a non-zero count, a
+ * workspace that is too small) return a negative code before any HIP call. */
+int frl_spectral_negatives(const float* spec, int64_t N, int C, const int32_t* offsets, int S, int n_per, const int32_t* draws, int64_t Q,
+                           float tau, float min_w, int64_t* pairs, float* dist, float* weights, int32_t* index_flag, frl_stream_t stream);
+size_t frl_pair_sims_workspace_bytes(int64_t T);
+int frl_pair_sims(const float* emb, int64_t N, int D, const int64_t* pairs, int64_t T, float* sims, double* stats, int32_t* index_flag, void* ws,
+                  size_t ws_bytes, frl_stream_t stream);
+
 /* ---- type-local spectral baseline (csrc/type_baseline.hip)----------------------------------------------------------------------
  * frl/training/representation/step.py:920-928.  z_k [N][K] float32 (the rank-K projection of the type embeddings, 1 <= K <= 64),
  * spec [N][T][C] float32 (T >= 1, 1 <= C <= 256, T * C < 2^31), N >= 2, 1 <= k <= min(64, N - 1).  Per anchor i: sim(i, j) =

@@ -108,6 +108,9 @@ SIGNATURES = {
     "frl_anchor_grid": (c_int, [P, I, I, I, I, I, I, P, I, P, P, P, P]),
     "frl_anchor_supplement": (c_int, [P, I, I, I, P, P, I, P, P, P, P, P, P]),
     "frl_anchor_inverse_frequency": (c_int, [P, P, I, I, I, P, I, P, P, P]),
+    "frl_spectral_negatives": (c_int, [P, L, I, P, I, I, P, L, F, F, P, P, P, P, P]),
+    "frl_pair_sims_workspace_bytes": (S, [L]),
+    "frl_pair_sims": (c_int, [P, L, I, P, L, P, P, P, P, S, P]),
     "frl_type_baseline_workspace_bytes": (S, [I, I]),
     "frl_type_baseline": (c_int, [P, P, I, I, I, I, I, P, P, P, P, S, P]),
     "frl_leakage_workspace_bytes": (S, [L, I, I]),

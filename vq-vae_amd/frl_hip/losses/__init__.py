@@ -8,5 +8,7 @@ from .phase_margin import (phase_recovery_discrimination_loss, compute_phase_spr
                            phase_spread_ranking_loss)
 from .phase_pairs import build_phase_pairs, build_phase_pairs_batched  # noqa: F401
 from .spatial_pairs import build_spatial_pairs, build_spatial_pairs_batched  # noqa: F401
+from .spectral_infonce import (cross_patch_negatives, pair_similarity, pair_similarity_stats, spectral_neg_tau_sweep,  # noqa: F401
+                               global_spectral_infonce)
 from .type_baseline import type_local_baseline, type_projection  # noqa: F401
 from .leakage import phase_type_leakage_loss  # noqa: F401

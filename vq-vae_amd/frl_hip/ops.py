@@ -1607,6 +1607,80 @@ def infonce_pair_grads(emb, pairs, sims, coef, gscale, nseg: int, temperature: f
 
 
 # ----------------------------------------------------------------------------------------------
+# cross-patch spectral negatives and pair similarities (csrc/spectral_negatives.hip)
+# ----------------------------------------------------------------------------------------------
+SPECTRAL_NEG_MAX_WIDTH = 256
+
+
+def _flag_for(device):
+    """(flag word handed to the kernel, check_now): a private word with FRL_HIP_CHECK_INDICES=1, the shared one otherwise."""
+    import os
+    check_now = os.environ.get("FRL_HIP_CHECK_INDICES", "0") == "1"
+    return (torch.zeros(1, dtype=torch.int32, device=device) if check_now else _index_flag(device)), check_now
+
+
+def _flag_done(flag: torch.Tensor, check_now: bool, what: str) -> None:
+    if check_now:
+        _index_flag(flag.device).bitwise_or_(flag)
+        if bool(flag.item()):
+            raise IndexError(what)
+
+
+@_timed("spectral_negatives")
+def spectral_negatives(spec: torch.Tensor, offsets: torch.Tensor, n_patches: int, n_per: int, draws: torch.Tensor, tau: float, min_w: float):
+    """spec [N, C] float32 (C <= 256), offsets [S + 1] int32 on the device, draws [Q, 2] int32 with Q = n_per S (S - 1) -> (pairs [Q, 2] int64,
+    dist [Q], weights [Q]) in one launch; include/frl_hip.h (frl_spectral_negatives) has the definitions.  A negative draw is taken as 0
+    and flagged for `index_errors()` (FRL_HIP_CHECK_INDICES=1: IndexError on the spot, one sync).  No host read."""
+    if not spec.is_cuda:
+        raise _lib.FrlHipError("spectral_negatives: tensors must live on the GPU (no CPU fallback)")
+    if spec.dim() != 2 or spec.dtype != torch.float32 or not spec.is_contiguous():
+        raise ValueError(f"spectral_negatives: spec must be a contiguous float32 [N, C] tensor, got {tuple(spec.shape)} {spec.dtype}")
+    n, c = spec.shape
+    s, n_per = int(n_patches), int(n_per)
+    q = n_per * s * (s - 1)
+    for t, shape, name in ((offsets, (s + 1,), "offsets"), (draws, (q, 2), "draws")):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != spec.device:
+            raise ValueError(f"spectral_negatives: {name} must be a contiguous int32 {list(shape)} tensor on the GPU of spec")
+    pairs = torch.empty(q, 2, dtype=torch.int64, device=spec.device)
+    dist = torch.empty(q, dtype=torch.float32, device=spec.device)
+    weights = torch.empty_like(dist)
+    if q == 0:
+        return pairs, dist, weights
+    flag, check_now = _flag_for(spec.device)
+    check(_lib.load().frl_spectral_negatives(_p(spec), n, c, _p(offsets), s, n_per, _p(draws), q, float(tau), float(min_w), _p(pairs), _p(dist),
+                                             _p(weights), _p(flag), _stream()), "frl_spectral_negatives")
+    _flag_done(flag, check_now, "spectral_negatives: a draw outside [0, 2^31) or patch bounds outside the spectral rows")
+    return pairs, dist, weights
+
+
+@_timed("pair_sims")
+def pair_sims(emb: torch.Tensor, pairs: torch.Tensor, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """emb [N, D] float32 (D <= 256), pairs [T, 2] int64 -> sims [T] = -|emb[a] - emb[b]|^2 / D.  stats: 4 float64 on the device that
+    receive (T, mean, unbiased std, 0) when T > 0; include/frl_hip.h (frl_pair_sims).  Rows out of range follow `sanitize_indices`,
+    inside the kernel.  No host read."""
+    if not emb.is_cuda:
+        raise _lib.FrlHipError("pair_sims: tensors must live on the GPU (no CPU fallback)")
+    if emb.dim() != 2 or emb.dtype != torch.float32 or not emb.is_contiguous():
+        raise ValueError(f"pair_sims: emb must be a contiguous float32 [N, D] tensor, got {tuple(emb.shape)} {emb.dtype}")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int64 or not pairs.is_contiguous() or pairs.device != emb.device:
+        raise ValueError("pair_sims: pairs must be a contiguous int64 [T, 2] tensor on the GPU of emb")
+    if stats is not None and (stats.dtype != torch.float64 or stats.numel() != 4 or not stats.is_contiguous() or stats.device != emb.device):
+        raise ValueError("pair_sims: stats must be 4 contiguous float64 on the GPU of emb")
+    n, d = emb.shape
+    t = pairs.shape[0]
+    sims = torch.empty(t, dtype=torch.float32, device=emb.device)
+    if t == 0:
+        return sims
+    lib = _lib.load()
+    nbytes = lib.frl_pair_sims_workspace_bytes(t) if stats is not None else 0
+    ws = workspace(nbytes, emb.device) if nbytes else None
+    flag, check_now = _flag_for(emb.device)
+    check(lib.frl_pair_sims(_p(emb), n, d, _p(pairs), t, _p(sims), _p(stats), _p(flag), _p(ws), nbytes, _stream()), "frl_pair_sims")
+    _flag_done(flag, check_now, f"pair_sims: pair row out of range for {n} rows")
+    return sims
+
+
+# ----------------------------------------------------------------------------------------------
 # VICReg variance-covariance loss (csrc/vicreg.hip)
 # ----------------------------------------------------------------------------------------------
 def _chk_vicreg(x: torch.Tensor, name: str):
