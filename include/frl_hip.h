@@ -724,6 +724,40 @@ int frl_leakage_fwd(const void* h, int h_dtype, const void* z, int z_dtype, int6
 int frl_leakage_bwd(const void* z, int z_dtype, const float* cmat, const float* centre, const float* stats, const float* g, int64_t N, int P,
                     int Dz, void* dh, int h_dtype, frl_stream_t stream);
 
+/* ---- diagonal-covariance Gaussian mixtures and the phase summary (csrc/gmm.hip) ---------------------------------------------------
+ * sklearn.mixture.GaussianMixture(covariance_type="diag") as frl/training/fit_gmm_clusters.py and fit_landscape_categories.py use it.
+ * All data float32, contiguous: X [N][D], optional row weights w [N] >= 0 (NULL: ones), weights pi [K], means mu [K][D], variances
+ * [K][D].  1 <= K <= 128, 1 <= D <= 128, K D <= 8192, K <= N < 2^31 (else -2).
+ * The iteration works on y = x - pivot (pivot [D]: the column mean of X, frl_gmm_pivot, once per fit) and carries the centred means
+ * means_c = mu - pivot next to mu, so data far from the origin loses nothing; the caller forms means_c once for initial parameters.
+ * frl_gmm_em_step (E): one pass over X.  lp[n][k] = log pi_k - (D log 2 pi + sum_d log var_kd + sum_d (x_nd - mu_kd)^2 / var_kd) / 2,
+ * lse_n = logsumexp_k lp, r = exp(lp - lse); each workgroup leaves sum w r, sum w r y, sum w r y^2, sum w lse and sum w in its slab of the
+ * workspace.  hard != 0: r is one-hot at argmax_k lp (ties: the lowest k) -- with unit variances and equal weights a Lloyd step.
+ * workgroups: 0 = the library's choice, else 1..4096 (the same value goes to frl_gmm_m_step; the workspace is sized for it).
+ * frl_gmm_m_step (M): adds the slabs in slab order in double, nk = sum w r + 10 * 2^-52, mu = pivot + S1 / nk,
+ * var = S2 / nk - (S1 / nk)^2 + reg_covar, pi = nk / sum nk.  mode 0 (EM) also appends lower_bound = sum w lse / sum w to
+ * history [max_iter] at index state[0], increments state[0] (iterations done) and sets state[1] (converged) when the bound moved by less
+ * than tol since the previous iteration; mode 1 (Lloyd) writes the means only, a component without a row keeps its mean; mode 2 writes
+ * all parameters from whatever responsibilities the last E pass used and leaves history and state alone.
+ * state: int32 [2], zeroed by the caller before a fit.  Once state[1] is set both calls leave every buffer untouched, so iterations
+ * may be enqueued without reading anything back and the result does not depend on when the host looks.
+ * frl_gmm_score: lse [N], labels [N] int32 (argmax_k lp, ties: the lowest k), optional resp [N][K].
+ * No float atomics: every result is bit-identical from run to run.  Workspace (16-byte aligned): frl_gmm_workspace_bytes.
+ * frl_phase_summary (_compute_phase_summary of fit_landscape_categories.py): z_phase [N][T][D] (T, D <= 64), ysfc [N][T] (NaN: not
+ * observed) -> summary [N][3 D] = mean over t with ysfc <= low_max | mean over t with ysfc >= high_min | mean over all t, the first two
+ * falling back to the third where no timestep matches; temporal_var [N] = the unbiased variance over t averaged over d (NaN at T = 1). */
+size_t frl_gmm_workspace_bytes(int64_t N, int D, int K, int workgroups);
+int frl_gmm_pivot(const float* X, int64_t N, int D, float* pivot, void* ws, size_t ws_bytes, frl_stream_t stream);
+int frl_gmm_em_step(const float* X, const float* w, int64_t N, int D, int K, const float* pivot, const float* weights, const float* means_c,
+                    const float* vars, int hard, int workgroups, const int* state, void* ws, size_t ws_bytes, frl_stream_t stream);
+int frl_gmm_m_step(int64_t N, int D, int K, const float* pivot, float* weights, float* means, float* means_c, float* vars, double reg_covar,
+                   double tol, int mode, double* history, int max_iter, int* state, int workgroups, void* ws, size_t ws_bytes,
+                   frl_stream_t stream);
+int frl_gmm_score(const float* X, int64_t N, int D, int K, const float* pivot, const float* weights, const float* means_c, const float* vars,
+                  float* lse, int* labels, float* resp, frl_stream_t stream);
+int frl_phase_summary(const float* z_phase, const float* ysfc, int64_t N, int T, int D, float low_max, float high_min, float* summary,
+                      float* temporal_var, frl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2200,3 +2200,158 @@ def spread_rank_gathered_bwd(emb: torch.Tensor, rows: torch.Tensor, lengths: tor
                                                    float(margin), float(delta), _p(pairstat), _p(g), _p(grows), _stream()),
           "frl_spread_rank_gathered_bwd")
     return grows
+
+
+# ----------------------------------------------------------------------------------------------
+# diagonal-covariance Gaussian mixtures and the phase summary (csrc/gmm.hip)
+# ----------------------------------------------------------------------------------------------
+GMM_MAX_K, GMM_MAX_D, GMM_MAX_KD, GMM_MAX_WORKGROUPS = 128, 128, 8192, 4096
+GMM_M_EM, GMM_M_LLOYD, GMM_M_INIT = 0, 1, 2
+PHASE_SUMMARY_MAX_T, PHASE_SUMMARY_MAX_D = 64, 64
+
+
+def chk_gmm_dims(n: int, d: int, k: int, name: str = "gmm", need_rows: bool = True):
+    """Every size limit of the frl_gmm_* calls (ValueError)."""
+    if not 1 <= k <= GMM_MAX_K:
+        raise ValueError(f"{name}: supports 1 <= K <= {GMM_MAX_K} components, got {k}")
+    if not 1 <= d <= GMM_MAX_D:
+        raise ValueError(f"{name}: supports 1 <= D <= {GMM_MAX_D} columns, got {d}")
+    if k * d > GMM_MAX_KD:
+        raise ValueError(f"{name}: supports K * D <= {GMM_MAX_KD}, got {k} * {d}")
+    if n >= 2 ** 31:
+        raise ValueError(f"{name}: supports N < 2^31 rows, got {n}")
+    if n < (k if need_rows else 1):
+        raise ValueError(f"{name}: needs N >= {'K' if need_rows else '1'} rows, got N = {n}, K = {k}")
+
+
+def chk_gmm(x: torch.Tensor, k: int, sample_weight: Optional[torch.Tensor] = None, workgroups: int = 0, name: str = "gmm",
+            need_rows: bool = True):
+    """Every limit of frl_gmm_em_step / frl_gmm_score that needs no device (ValueError)."""
+    if x.dim() != 2:
+        raise ValueError(f"{name}: expected X [N, D], got {tuple(x.shape)}")
+    chk_gmm_dims(x.shape[0], x.shape[1], int(k), name, need_rows)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{name}: X must be a contiguous float32 tensor, got {x.dtype} stride {x.stride()}")
+    if sample_weight is not None and (sample_weight.dtype != torch.float32 or sample_weight.shape != (x.shape[0],)
+                                      or not sample_weight.is_contiguous()):
+        raise ValueError(f"{name}: sample_weight must be a contiguous float32 [N] tensor, got {sample_weight.dtype} {tuple(sample_weight.shape)}")
+    if not 0 <= int(workgroups) <= GMM_MAX_WORKGROUPS:
+        raise ValueError(f"{name}: workgroups must be in 0..{GMM_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+
+
+def _chk_gmm_params(name: str, device, k: int, d: int, **tensors):
+    for what, (t, shape) in tensors.items():
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous float32 {shape} tensor, got {t.dtype} {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+        if t.device != device:
+            raise ValueError(f"{name}: {what} must be on the device of X")
+
+
+def gmm_workspace(n: int, d: int, k: int, device, workgroups: int = 0) -> torch.Tensor:
+    """A workspace of one fit: it carries the partial sums from gmm_em_step to gmm_m_step, so it is not the shared scratch buffer."""
+    chk_gmm_dims(n, d, k, "gmm_workspace", need_rows=False)
+    if not torch.device(device).type == "cuda":
+        raise _lib.FrlHipError("gmm_workspace: the device must be a GPU (no CPU fallback)")
+    return torch.empty(max(_lib.load().frl_gmm_workspace_bytes(n, d, k, int(workgroups)), 256), dtype=torch.uint8, device=device)
+
+
+@_timed("gmm_pivot")
+def gmm_pivot(x: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """X [N, D] f32 -> its column means [D] f32 (summed in double in a fixed order)."""
+    chk_gmm(x, 1, name="gmm_pivot", need_rows=False)
+    if not x.is_cuda:
+        raise _lib.FrlHipError("gmm_pivot: tensors must live on the GPU (no CPU fallback)")
+    pivot = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
+    check(_lib.load().frl_gmm_pivot(_p(x), x.shape[0], x.shape[1], _p(pivot), _p(ws), ws.numel(), _stream()), "frl_gmm_pivot")
+    return pivot
+
+
+@_timed("gmm_em_step")
+def gmm_em_step(x: torch.Tensor, sample_weight: Optional[torch.Tensor], pivot: torch.Tensor, weights: torch.Tensor, means_c: torch.Tensor,
+                variances: torch.Tensor, state: torch.Tensor, ws: torch.Tensor, hard: bool = False, workgroups: int = 0) -> None:
+    """The E pass of one iteration (include/frl_hip.h: frl_gmm_em_step): the partial sums land in ws for gmm_m_step.  No host read."""
+    k = weights.shape[0] if weights.dim() == 1 else -1
+    chk_gmm(x, k, sample_weight, workgroups, "gmm_em_step")
+    if not x.is_cuda:
+        raise _lib.FrlHipError("gmm_em_step: tensors must live on the GPU (no CPU fallback)")
+    d = x.shape[1]
+    _chk_gmm_params("gmm_em_step", x.device, k, d, pivot=(pivot, (d,)), weights=(weights, (k,)), means_c=(means_c, (k, d)),
+                    variances=(variances, (k, d)))
+    if state.dtype != torch.int32 or state.numel() != 2 or state.device != x.device:
+        raise ValueError("gmm_em_step: state must be an int32 [2] tensor on the device of X")
+    check(_lib.load().frl_gmm_em_step(_p(x), _p(sample_weight), x.shape[0], d, k, _p(pivot), _p(weights), _p(means_c), _p(variances),
+                                      1 if hard else 0, int(workgroups), _p(state), _p(ws), ws.numel(), _stream()), "frl_gmm_em_step")
+
+
+@_timed("gmm_m_step")
+def gmm_m_step(n: int, pivot: torch.Tensor, weights: torch.Tensor, means: torch.Tensor, means_c: torch.Tensor, variances: torch.Tensor,
+               state: torch.Tensor, ws: torch.Tensor, history: Optional[torch.Tensor] = None, reg_covar: float = 1e-6, tol: float = 1e-3,
+               mode: int = GMM_M_EM, workgroups: int = 0) -> None:
+    """The M pass (include/frl_hip.h: frl_gmm_m_step): parameters in place; mode GMM_M_EM also appends the lower bound to `history`
+    (float64 [max_iter]) and keeps the iteration count and the convergence flag in `state`.  No host read."""
+    k, d = means.shape
+    chk_gmm_dims(int(n), d, k, "gmm_m_step")
+    if not 0 <= int(workgroups) <= GMM_MAX_WORKGROUPS:
+        raise ValueError(f"gmm_m_step: workgroups must be in 0..{GMM_MAX_WORKGROUPS}, got {workgroups}")
+    _chk_gmm_params("gmm_m_step", means.device, k, d, pivot=(pivot, (d,)), weights=(weights, (k,)), means=(means, (k, d)),
+                    means_c=(means_c, (k, d)), variances=(variances, (k, d)))
+    max_iter = 0
+    if mode == GMM_M_EM:
+        if history is None or history.dtype != torch.float64 or history.dim() != 1 or history.device != means.device or history.numel() < 1:
+            raise ValueError("gmm_m_step: the EM mode needs a float64 [max_iter] history on the device of the parameters")
+        max_iter = history.numel()
+    check(_lib.load().frl_gmm_m_step(int(n), d, k, _p(pivot), _p(weights), _p(means), _p(means_c), _p(variances), float(reg_covar), float(tol),
+                                     int(mode), _p(history), max_iter, _p(state), int(workgroups), _p(ws), ws.numel(), _stream()),
+          "frl_gmm_m_step")
+
+
+@_timed("gmm_score")
+def gmm_score(x: torch.Tensor, pivot: torch.Tensor, weights: torch.Tensor, means_c: torch.Tensor, variances: torch.Tensor,
+              want_resp: bool = False):
+    """-> (lse f32 [N], labels int32 [N], resp f32 [N, K] | None) of X under the mixture (include/frl_hip.h: frl_gmm_score)."""
+    k = weights.shape[0] if weights.dim() == 1 else -1
+    chk_gmm(x, k, name="gmm_score", need_rows=False)
+    if not x.is_cuda:
+        raise _lib.FrlHipError("gmm_score: tensors must live on the GPU (no CPU fallback)")
+    n, d = x.shape
+    _chk_gmm_params("gmm_score", x.device, k, d, pivot=(pivot, (d,)), weights=(weights, (k,)), means_c=(means_c, (k, d)),
+                    variances=(variances, (k, d)))
+    lse = torch.empty(n, dtype=torch.float32, device=x.device)
+    labels = torch.empty(n, dtype=torch.int32, device=x.device)
+    resp = torch.empty(n, k, dtype=torch.float32, device=x.device) if want_resp else None
+    check(_lib.load().frl_gmm_score(_p(x), n, d, k, _p(pivot), _p(weights), _p(means_c), _p(variances), _p(lse), _p(labels), _p(resp), _stream()),
+          "frl_gmm_score")
+    return lse, labels, resp
+
+
+def chk_phase_summary(z_phase: torch.Tensor, ysfc: torch.Tensor):
+    """Every limit of frl_phase_summary that needs no device (ValueError)."""
+    if z_phase.dim() != 3 or ysfc.dim() != 2 or tuple(ysfc.shape) != tuple(z_phase.shape[:2]) or z_phase.shape[0] < 1:
+        raise ValueError(f"phase_summary: expected z_phase [N, T, D] and ysfc [N, T] with N >= 1, got {tuple(z_phase.shape)} and {tuple(ysfc.shape)}")
+    if not 1 <= z_phase.shape[1] <= PHASE_SUMMARY_MAX_T:
+        raise ValueError(f"phase_summary: supports 1 <= T <= {PHASE_SUMMARY_MAX_T} timesteps, got {z_phase.shape[1]}")
+    if not 1 <= z_phase.shape[2] <= PHASE_SUMMARY_MAX_D:
+        raise ValueError(f"phase_summary: supports 1 <= D <= {PHASE_SUMMARY_MAX_D} channels, got {z_phase.shape[2]}")
+    if z_phase.shape[0] >= 2 ** 31:
+        raise ValueError("phase_summary: supports N < 2^31 rows")
+    for t, what in ((z_phase, "z_phase"), (ysfc, "ysfc")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"phase_summary: {what} must be a contiguous float32 tensor, got {t.dtype} stride {t.stride()}")
+
+
+@_timed("phase_summary")
+def phase_summary(z_phase: torch.Tensor, ysfc: torch.Tensor, low_max: float = 1.0, high_min: float = 5.0):
+    """z_phase [N, T, D], ysfc [N, T] (NaN: unobserved) -> (summary [N, 3 D], temporal_var [N]); include/frl_hip.h: frl_phase_summary."""
+    chk_phase_summary(z_phase, ysfc)
+    if not z_phase.is_cuda or not ysfc.is_cuda:
+        raise _lib.FrlHipError("phase_summary: tensors must live on the GPU (no CPU fallback)")
+    if z_phase.device != ysfc.device:
+        raise ValueError("phase_summary: z_phase and ysfc must be on one device")
+    n, t, d = z_phase.shape
+    summary = torch.empty(n, 3 * d, dtype=torch.float32, device=z_phase.device)
+    tvar = torch.empty(n, dtype=torch.float32, device=z_phase.device)
+    check(_lib.load().frl_phase_summary(_p(z_phase), _p(ysfc), n, t, d, float(low_max), float(high_min), _p(summary), _p(tvar), _stream()),
+          "frl_phase_summary")
+    return summary, tvar
