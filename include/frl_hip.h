@@ -758,6 +758,32 @@ int frl_gmm_score(const float* X, int64_t N, int D, int K, const float* pivot, c
 int frl_phase_summary(const float* z_phase, const float* ysfc, int64_t N, int T, int D, float low_max, float high_min, float* summary,
                       float* temporal_var, frl_stream_t stream);
 
+/* ---- closed-form linear probes (csrc/probe.hip) ----------------------------------------------------------------------------------
+ * The streamed ridge fit and the evaluation of frl/training/fit_linear_probe.py and fit_phase_linear_probe.py.
+ * An observation is (b, t, p) with b < B, t < T, p < P.  Feature columns come from A [B][Ta][P][Da] and, when Db > 0, Bs [B][Tb][P][Db]
+ * (Bs NULL exactly when Db = 0), targets from Y [B][Ty][P][Cy]; all row-major float32 with Ta, Tb, Ty each 1 (the row is shared by all
+ * t) or T.  mask [B][P] uint8 is shared over t; an observation counts where it is non-zero.
+ * Limits (else -2): D = Da + Db <= 128, 1 <= Cy <= 16, B T P < 2^31.  C = D + Cy.
+ * frl_probe_pivot: pivot [C] = the masked column means of [x | y] of this call, summed in double in a fixed order, rounded to float32
+ * (zeros when nothing is unmasked).
+ * frl_probe_accumulate: with v = [x - pivot_x | y - pivot_y | m] (subtracted in float32; the whole row is zero where the mask is),
+ * S [C+1][C+1] (double, both triangles) += v^T v and *n (int64) += the number of unmasked observations.  Tiles of 64 pixels whose
+ * mask is all zero are not read.  The products are exact float32 fmaf chains inside a workgroup; the workgroups' slabs are added in a
+ * fixed order in double.  workgroups: 0 = the library's choice, else 1..4096.  S and n are zeroed by the caller before the first call.
+ * frl_probe_evaluate: pred_c = bc_c + sum_d (x_d - pivot_d) Wc[d][c], a float32 fmaf chain in d order (Wc [D][Cy], bc [Cy]); over the
+ * unmasked observations E [Cy][3] (double) += (sum (pred - y)^2, sum (y - pivot_y), sum (y - pivot_y)^2) and *n += their number.
+ * pred (optional) [B][T][P][Cy] receives the prediction of every observation, masked or not; without it all-zero mask tiles are skipped.
+ * No float atomics: every result is bit-identical from run to run.  Workspace (16-byte aligned): frl_probe_workspace_bytes. */
+size_t frl_probe_workspace_bytes(int D, int Cy, int workgroups);
+int frl_probe_pivot(const float* A, int Ta, int Da, const float* Bs, int Tb, int Db, const float* Y, int Ty, int Cy, const unsigned char* mask,
+                    int B, int T, int64_t P, float* pivot, void* ws, size_t ws_bytes, frl_stream_t stream);
+int frl_probe_accumulate(const float* A, int Ta, int Da, const float* Bs, int Tb, int Db, const float* Y, int Ty, int Cy,
+                         const unsigned char* mask, int B, int T, int64_t P, const float* pivot, int workgroups, double* S, int64_t* n, void* ws,
+                         size_t ws_bytes, frl_stream_t stream);
+int frl_probe_evaluate(const float* A, int Ta, int Da, const float* Bs, int Tb, int Db, const float* Y, int Ty, int Cy, const unsigned char* mask,
+                       int B, int T, int64_t P, const float* pivot, const float* Wc, const float* bc, int workgroups, double* E, int64_t* n,
+                       float* pred, void* ws, size_t ws_bytes, frl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

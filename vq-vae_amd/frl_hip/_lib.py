@@ -122,6 +122,10 @@ SIGNATURES = {
     "frl_gmm_m_step": (c_int, [L, I, I, P, P, P, P, P, D, D, I, P, I, P, I, P, S, P]),
     "frl_gmm_score": (c_int, [P, L, I, I, P, P, P, P, P, P, P, P]),
     "frl_phase_summary": (c_int, [P, P, L, I, I, F, F, P, P, P]),
+    "frl_probe_workspace_bytes": (S, [I, I, I]),
+    "frl_probe_pivot": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, P, S, P]),
+    "frl_probe_accumulate": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, I, P, P, P, S, P]),
+    "frl_probe_evaluate": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, P, P, I, P, P, P, P, S, P]),
     "frl_host_parallel_copy": (c_int, [P, P, S, I]),
     "frl_normalize_chunk_tiles": (c_int, [P, I, I, I, I, I, P, I, I, P, P, I, P, P]),
     "frl_conv3x3_fwd": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P, S, P]),

@@ -2355,3 +2355,105 @@ def phase_summary(z_phase: torch.Tensor, ysfc: torch.Tensor, low_max: float = 1.
     check(_lib.load().frl_phase_summary(_p(z_phase), _p(ysfc), n, t, d, float(low_max), float(high_min), _p(summary), _p(tvar), _stream()),
           "frl_phase_summary")
     return summary, tvar
+
+
+# ----------------------------------------------------------------------------------------------
+# closed-form linear probes (csrc/probe.hip)
+# ----------------------------------------------------------------------------------------------
+PROBE_MAX_D, PROBE_MAX_CY, PROBE_MAX_WORKGROUPS = 128, 16, 4096
+
+
+def chk_probe_dims(d: int, cy: int, workgroups: int = 0, name: str = "probe"):
+    """The size limits of the frl_probe_* calls that need no data (ValueError)."""
+    if not 1 <= int(d) <= PROBE_MAX_D:
+        raise ValueError(f"{name}: supports 1 <= D <= {PROBE_MAX_D} feature columns, got {d}")
+    if not 1 <= int(cy) <= PROBE_MAX_CY:
+        raise ValueError(f"{name}: supports 1 <= Cy <= {PROBE_MAX_CY} targets, got {cy}")
+    if not 0 <= int(workgroups) <= PROBE_MAX_WORKGROUPS:
+        raise ValueError(f"{name}: workgroups must be in 0..{PROBE_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+
+
+def chk_probe(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor, mask: torch.Tensor, workgroups: int = 0, name: str = "probe"):
+    """Every limit of the frl_probe_* calls that needs no device (ValueError) -> (B, T, P, Da, Db, Cy)."""
+    for what, t in (("A", a), ("B", bs), ("Y", y)):
+        if t is None:
+            continue
+        if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous float32 [B, T_s, P, C] tensor, got {t.dtype} {tuple(t.shape)} stride {t.stride()}")
+    if mask.dim() != 2 or mask.dtype != torch.uint8 or not mask.is_contiguous():
+        raise ValueError(f"{name}: mask must be a contiguous uint8 [B, P] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    b, p = mask.shape
+    t = max(s.shape[1] for s in (a, bs, y) if s is not None)
+    for what, s in (("A", a), ("B", bs), ("Y", y)):
+        if s is not None and (s.shape[0] != b or s.shape[2] != p or s.shape[1] not in (1, t)):
+            raise ValueError(f"{name}: {what} {tuple(s.shape)} does not match B = {b}, T in (1, {t}), P = {p}")
+    da, db, cy = a.shape[3], 0 if bs is None else bs.shape[3], y.shape[3]
+    chk_probe_dims(da + db, cy, workgroups, name)
+    if b < 1 or p < 1 or t < 1 or da < 1 or (bs is not None and db < 1):
+        raise ValueError(f"{name}: empty input, B = {b}, T = {t}, P = {p}, Da = {da}")
+    if b * t * p >= 2 ** 31:
+        raise ValueError(f"{name}: supports B * T * P < 2^31 observations, got {b * t * p}")
+    for s in (a, bs, y, mask):
+        if s is not None and not s.is_cuda:
+            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+        if s is not None and s.device != a.device:
+            raise ValueError(f"{name}: all tensors must be on one device")
+    return b, t, p, da, db, cy
+
+
+def _chk_probe_vec(name: str, what: str, t: torch.Tensor, shape, dtype, device):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} {tuple(shape)} tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def probe_workspace(d: int, cy: int, device, workgroups: int = 0) -> torch.Tensor:
+    """A workspace for the frl_probe_* calls of one probe (slabs of partial sums between a pass and its reduction)."""
+    chk_probe_dims(d, cy, workgroups, "probe_workspace")
+    if not torch.device(device).type == "cuda":
+        raise _lib.FrlHipError("probe_workspace: the device must be a GPU (no CPU fallback)")
+    return torch.empty(max(_lib.load().frl_probe_workspace_bytes(int(d), int(cy), int(workgroups)), 256), dtype=torch.uint8, device=device)
+
+
+def _probe_args(a, bs, y, mask, dims):
+    b, t, p, da, db, cy = dims
+    return (_p(a), a.shape[1], da, _p(bs), 1 if bs is None else bs.shape[1], db, _p(y), y.shape[1], cy, _p(mask), b, t, p)
+
+
+@_timed("probe_pivot")
+def probe_pivot(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor, mask: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """-> pivot f32 [D + Cy]: the masked column means of [x | y] (include/frl_hip.h: frl_probe_pivot)."""
+    dims = chk_probe(a, bs, y, mask, 0, "probe_pivot")
+    pivot = torch.empty(dims[3] + dims[4] + dims[5], dtype=torch.float32, device=a.device)
+    check(_lib.load().frl_probe_pivot(*_probe_args(a, bs, y, mask, dims), _p(pivot), _p(ws), ws.numel(), _stream()), "frl_probe_pivot")
+    return pivot
+
+
+@_timed("probe_accumulate")
+def probe_accumulate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor, mask: torch.Tensor, pivot: torch.Tensor, s: torch.Tensor,
+                     n: torch.Tensor, ws: torch.Tensor, workgroups: int = 0) -> None:
+    """S f64 [C+1, C+1] += v^T v, n int64 [1] += the unmasked count (include/frl_hip.h: frl_probe_accumulate).  No host read."""
+    dims = chk_probe(a, bs, y, mask, workgroups, "probe_accumulate")
+    c = dims[3] + dims[4] + dims[5]
+    _chk_probe_vec("probe_accumulate", "pivot", pivot, (c,), torch.float32, a.device)
+    _chk_probe_vec("probe_accumulate", "S", s, (c + 1, c + 1), torch.float64, a.device)
+    _chk_probe_vec("probe_accumulate", "n", n, (1,), torch.int64, a.device)
+    check(_lib.load().frl_probe_accumulate(*_probe_args(a, bs, y, mask, dims), _p(pivot), int(workgroups), _p(s), _p(n), _p(ws), ws.numel(),
+                                           _stream()), "frl_probe_accumulate")
+
+
+@_timed("probe_evaluate")
+def probe_evaluate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor, mask: torch.Tensor, pivot: torch.Tensor, wc: torch.Tensor,
+                   bc: torch.Tensor, e: torch.Tensor, n: torch.Tensor, ws: torch.Tensor, want_pred: bool = False, workgroups: int = 0):
+    """E f64 [Cy, 3] += (SSE, sum (y - q), sum (y - q)^2), n int64 [1] += the unmasked count; -> pred f32 [B, T, P, Cy] | None
+    (include/frl_hip.h: frl_probe_evaluate).  No host read."""
+    dims = chk_probe(a, bs, y, mask, workgroups, "probe_evaluate")
+    b, t, p, da, db, cy = dims
+    _chk_probe_vec("probe_evaluate", "pivot", pivot, (da + db + cy,), torch.float32, a.device)
+    _chk_probe_vec("probe_evaluate", "Wc", wc, (da + db, cy), torch.float32, a.device)
+    _chk_probe_vec("probe_evaluate", "bc", bc, (cy,), torch.float32, a.device)
+    _chk_probe_vec("probe_evaluate", "E", e, (cy, 3), torch.float64, a.device)
+    _chk_probe_vec("probe_evaluate", "n", n, (1,), torch.int64, a.device)
+    pred = torch.empty(b, t, p, cy, dtype=torch.float32, device=a.device) if want_pred else None
+    check(_lib.load().frl_probe_evaluate(*_probe_args(a, bs, y, mask, dims), _p(pivot), _p(wc), _p(bc), int(workgroups), _p(e), _p(n), _p(pred),
+                                         _p(ws), ws.numel(), _stream()), "frl_probe_evaluate")
+    return pred
