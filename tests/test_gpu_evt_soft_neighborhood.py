@@ -175,6 +175,23 @@ def test_wide_shape_matches_the_restatement(metrics):
     assert torch.equal(loss, loss2) and torch.equal(g, g2)
 
 
+def test_long_segment_matches_the_restatement(metrics):
+    # one segment of 300 rows over three codes: more rows than the 256 threads that sum a segment's rows, ten row tiles, five column tiles
+    metric = metrics["b"]
+    kept = sorted(metric.valid_codes)
+    emb = EC.make_embeddings(300, 4, 433)
+    codes = EC.make_codes(300, 434, kept[:3])
+    kw = dict(tau_ref=0.3, tau_learned=0.7, min_valid_anchors=4)
+    want_l, want_s, want_g = EC.evt_f64(emb, EC.code_index(codes, kept), metric._S, metric._freq_weights, [0, 300], **kw)
+    loss, stats, g = _run(emb, codes, metric, kw)
+    assert stats["n_rows_active"] == 300
+    _check_loss(loss, want_l[0], "N=300 D=4")
+    _check_stats(stats, want_s[0], "N=300 D=4")
+    _check_grad(g, want_g.numpy(), "N=300 D=4")
+    loss2, _, g2 = _run(emb, codes, metric, kw)
+    assert torch.equal(loss, loss2) and torch.equal(g, g2)
+
+
 def test_out_of_range_index_is_unknown_and_flagged(golden_dir, metrics):
     from frl_hip import ops
     fx, metric, kw, emb, codes = _case(golden_dir, metrics, "a")

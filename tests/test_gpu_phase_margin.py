@@ -100,9 +100,10 @@ def test_recovery_matches_reference_fixture(golden_dir, case):
 
 
 @pytest.mark.parametrize("n,t,d,margin", [(5, 1, 1, 0.5), (7, 2, 3, 0.5), (9, 32, 100, 0.5), (6, 32, 128, 0.5), (5, 32, 256, 0.5), (3, 17, 255, 0.5),
-                                          (260, 15, 12, 25.0)])
+                                          (260, 15, 12, 25.0), (1030, 2, 3, 0.5)])
 def test_recovery_shapes_match_the_restatement(n, t, d, margin):
-    # the widths at which four, three, two and one pixel share a workgroup, forward and backward; margin 25: softplus past its threshold
+    # the widths at which four, three, two and one pixel share a workgroup, forward and backward; margin 25: softplus past its threshold;
+    # N = 1030: more pixels than the 1024 threads of the final reduction
     z = SC.make_points(n, t, d, seed=n + t + d, scale=0.05)
     ysfc = PC.plant_invalid(SC.make_ysfc(n, t, seed=n * t + d), seed=d, nan_frac=0.1, neg_frac=0.05)
     ysfc[0, :] = float("nan")

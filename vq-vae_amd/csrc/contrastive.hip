@@ -12,6 +12,7 @@
 // scatter (rows of the embedding matrix that occur in many pairs) is the same primitive: frl_segment_sum_rows over a sorted key.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
+#include "frl_loss.hpp"
 #include <math.h>
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -55,12 +56,6 @@ __global__ __launch_bounds__(256) void segment_sum_rows_kernel(const float* __re
 // per pair: similarity (l2: -|a-b|^2 / D, cosine, dot) and logit = log(w) + sim / t.  One 16-lane group per pair.
 // ---------------------------------------------------------------------------------------------------------------------------
 enum { FRL_SIM_L2 = 0, FRL_SIM_COSINE = 1, FRL_SIM_DOT = 2 };
-
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void pair_logits_kernel(const float* __restrict__ emb, int D, const int64_t* __restrict__ pairs,
                                                           const float* __restrict__ weights, int64_t T, float inv_t, int sim_kind,
@@ -178,12 +173,7 @@ __global__ __launch_bounds__(256) void pair_grad_rows_kernel(const float* __rest
   }
 }
 
-static unsigned ct_grid(int64_t work, int per_block) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
+static unsigned ct_grid(int64_t work, int per_block) { return frl_grid(work, per_block, 2048); }
 
 extern "C" {
 

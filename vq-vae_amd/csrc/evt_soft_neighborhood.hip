@@ -30,6 +30,7 @@
 // gradient row is written once, by one workgroup, in a fixed order: no float atomics, bit-identical from run to run.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
+#include "frl_loss.hpp"
 #include <math.h>
 #include <stdio.h>
 
@@ -213,15 +214,7 @@ __global__ __launch_bounds__(256) void evt_reduce_kernel(const float* __restrict
       s[6] += ncf;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 11; ++k) {
-    const double v = wave_sum_d(s[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 11) red[0][threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-  __syncthreads();
+  block_sum_d<11, 4>(s, red);
   if (threadIdx.x == 0) {
     const double W = red[0][1];
     const bool live = red[0][2] >= (double)min_valid && W > 0.0;
@@ -383,8 +376,7 @@ int frl_evt_soft_nbr_fwd(const void* emb, int emb_dtype, int64_t N, int D, const
   int rc = ev_check("evt_soft_nbr_fwd", emb, emb_dtype, N, D, idx, S, w, K, seg, seg_host, nseg, inv_tau_ref, inv_tau_learned, &maxlen);
   if (rc) return rc;
   if (!rowstat || !segout || !segstat) return frl_fail(-2, "evt_soft_nbr_fwd: NULL argument");
-  rc = emb_dtype == FRL_F32 ? ev_launch_fwd<float>(emb, D, idx, S, K, seg, nseg, maxlen, inv_tau_ref, inv_tau_learned, rowstat, flag, stream)
-                            : ev_launch_fwd<bf16>(emb, D, idx, S, K, seg, nseg, maxlen, inv_tau_ref, inv_tau_learned, rowstat, flag, stream);
+  FRL_BY_DTYPE(emb_dtype, T, rc = ev_launch_fwd<T>(emb, D, idx, S, K, seg, nseg, maxlen, inv_tau_ref, inv_tau_learned, rowstat, flag, stream));
   if (rc) return rc;
   FRL_LAUNCH(evt_reduce_kernel, dim3((unsigned)nseg), dim3(256), 0, stream, (const float*)rowstat, idx, w, K, seg, min_valid_anchors, segout,
              segstat);
@@ -399,9 +391,8 @@ int frl_evt_soft_nbr_bwd(const void* emb, int emb_dtype, int64_t N, int D, const
   int rc = ev_check("evt_soft_nbr_bwd", emb, emb_dtype, N, D, idx, S, w, K, seg, seg_host, nseg, inv_tau_ref, inv_tau_learned, &maxlen);
   if (rc) return rc;
   if (!rowstat || !segout || !gup || !grad) return frl_fail(-2, "evt_soft_nbr_bwd: NULL argument");
-  rc = emb_dtype == FRL_F32
-           ? ev_launch_bwd<float>(emb, D, idx, S, w, K, seg, nseg, maxlen, inv_tau_ref, inv_tau_learned, rowstat, segout, gup, seg_weights, grad, stream)
-           : ev_launch_bwd<bf16>(emb, D, idx, S, w, K, seg, nseg, maxlen, inv_tau_ref, inv_tau_learned, rowstat, segout, gup, seg_weights, grad, stream);
+  FRL_BY_DTYPE(emb_dtype, T, rc = ev_launch_bwd<T>(emb, D, idx, S, w, K, seg, nseg, maxlen, inv_tau_ref, inv_tau_learned, rowstat, segout, gup,
+                                                   seg_weights, grad, stream));
   if (rc) return rc;
   return frl_check_launch("evt_soft_nbr_bwd");
 }

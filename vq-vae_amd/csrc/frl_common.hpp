@@ -122,6 +122,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // XCD-aware block remap: blocks that share an XCD (b % 8 equal) get a contiguous chunk of the
 // logical grid so neighbouring tiles hit the same L2.  Bijective for any grid size.

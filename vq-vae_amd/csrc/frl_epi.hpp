@@ -122,6 +122,13 @@ struct CodeEpi {
   }
 };
 
+// summed moments of the VICReg and leakage losses (vicreg.hip, leakage.hip): the slab sum as it is, read by the finalise kernel of the
+// same call, so not deferrable
+struct CopyEpi {
+  float* dst;
+  __device__ void operator()(int64_t i, float s) const { dst[i] = s; }
+};
+
 // Kind tags of the deferrable epilogues (0 = not deferrable: the result is consumed inside the same C-ABI call)
 template <class Epi> struct FrlEpiKind { static constexpr int id = 0; };
 template <> struct FrlEpiKind<ThEpi> { static constexpr int id = 1; };

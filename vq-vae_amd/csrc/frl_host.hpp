@@ -47,6 +47,30 @@ void frl_timing_end(hipStream_t st);
     if (_e != hipSuccess) return frl_fail(-100 - (int)_e, hipGetErrorString(_e)); \
   } while (0)
 
+// grid of a grid-stride kernel: ceil(work / per_block) workgroups, at least 1 and at most cap
+static inline unsigned frl_grid(int64_t work, int per_block, int cap) {
+  int64_t g = (work + per_block - 1) / per_block;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+// moment kernels that give each workgroup a contiguous range of rows, staged rows_per_tile at a time (vicreg.hip, leakage.hip): the
+// number of workgroups (= slabs), and the rows of one workgroup, a whole number of tiles
+static inline int frl_moment_wgs(int64_t N, int rows_per_tile, int max_wgs) { return (int)frl_grid(N, rows_per_tile, max_wgs); }
+static inline int64_t frl_moment_rows_per_wg(int64_t N, int rows_per_tile, int max_wgs) {
+  const int nwg = frl_moment_wgs(N, rows_per_tile, max_wgs);
+  return ((N + nwg - 1) / nwg + rows_per_tile - 1) / rows_per_tile * rows_per_tile;
+}
+
+// Runs the statement(s) once with T naming the element type of a FRL_F32 / FRL_BF16 dtype that the caller has validated, so the argument
+// list of a launch templated on the type is written once:  FRL_BY_DTYPE(dtype, T, rc = launch<T, true>(x, n, stream));
+#define FRL_BY_DTYPE(dtype, T, ...)                       \
+  do {                                                    \
+    if ((dtype) == FRL_F32) { using T = float; __VA_ARGS__; } \
+    else { using T = bf16; __VA_ARGS__; }                 \
+  } while (0)
+
 // internal cross-file dispatchers
 int frl_pw_dispatch(const void* x, const void* xmask, int mask_act, const float* w, int64_t so, int64_t si,
                     const float* bias, void* y, int64_t P, int Cin, int Cout, int act, int dtype, void* ws, size_t ws_bytes,

@@ -99,11 +99,6 @@ __global__ __launch_bounds__(256) void leakage_moments_kernel(const TH* __restri
   if (tid < P) my[(int64_t)P * Dz + tid] = sh;
 }
 
-struct LkCopyEpi {
-  float* dst;
-  __device__ void operator()(int64_t i, float s) const { dst[i] = s; }
-};
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // finalise (one workgroup): m = [P*Dz] G | [P] Sh | [Dz] Sz  ->  stats [2] = loss, 1 / (max(N-1, 1) * loss) (0 where loss == 0: the
 // backward then writes zeros); cmat [P*Dz] = C and centre [2][Dz] = pz | mean_z - pz when a gradient is wanted.  The combination runs in
@@ -177,22 +172,13 @@ __global__ __launch_bounds__(256) void leakage_bwd_kernel(const TZ* __restrict__
   }
 }
 
-static int lk_nwg(int64_t N) {
-  int64_t n = (N + LK_ROWS - 1) / LK_ROWS;
-  if (n > LK_MAX_WGS) n = LK_MAX_WGS;
-  if (n < 1) n = 1;
-  return (int)n;
-}
-static int64_t lk_rows_per_wg(int64_t N, int nwg) {
-  const int64_t rows = (N + nwg - 1) / nwg;
-  return (rows + LK_ROWS - 1) / LK_ROWS * LK_ROWS;
-}
+static int lk_nwg(int64_t N) { return frl_moment_wgs(N, LK_ROWS, LK_MAX_WGS); }
 static size_t lk_slab_floats(int P, int Dz) { return (size_t)P * Dz + P + Dz; }
 
 template <typename TH, typename TZ>
 static void lk_launch_moments(const void* h, const void* z, float* slab, int64_t N, int P, int Dz, hipStream_t st) {
   const int nwg = lk_nwg(N);
-  const int64_t rows = lk_rows_per_wg(N, nwg);
+  const int64_t rows = frl_moment_rows_per_wg(N, LK_ROWS, LK_MAX_WGS);
   if (P <= 16) FRL_LAUNCH((leakage_moments_kernel<TH, TZ, 8>), dim3(nwg), dim3(256), 0, st, (const TH*)h, (const TZ*)z, slab, N, P, Dz, rows);
   else if (P <= 32) FRL_LAUNCH((leakage_moments_kernel<TH, TZ, 16>), dim3(nwg), dim3(256), 0, st, (const TH*)h, (const TZ*)z, slab, N, P, Dz, rows);
   else FRL_LAUNCH((leakage_moments_kernel<TH, TZ, 32>), dim3(nwg), dim3(256), 0, st, (const TH*)h, (const TZ*)z, slab, N, P, Dz, rows);
@@ -242,14 +228,8 @@ int frl_leakage_fwd(const void* h, int h_dtype, const void* z, int z_dtype, int6
   const int64_t n = (int64_t)lk_slab_floats(P, Dz);
   float* slab = (float*)ws;
   float* mom = slab + (int64_t)nwg * n;
-  if (h_dtype == FRL_F32) {
-    if (z_dtype == FRL_F32) lk_launch_moments<float, float>(h, z, slab, N, P, Dz, stream);
-    else lk_launch_moments<float, bf16>(h, z, slab, N, P, Dz, stream);
-  } else {
-    if (z_dtype == FRL_F32) lk_launch_moments<bf16, float>(h, z, slab, N, P, Dz, stream);
-    else lk_launch_moments<bf16, bf16>(h, z, slab, N, P, Dz, stream);
-  }
-  launch_slab_reduce<float, LkCopyEpi>(slab, nwg, n, LkCopyEpi{mom}, stream);
+  FRL_BY_DTYPE(h_dtype, TH, FRL_BY_DTYPE(z_dtype, TZ, lk_launch_moments<TH, TZ>(h, z, slab, N, P, Dz, stream)));
+  launch_slab_reduce<float, CopyEpi>(slab, nwg, n, CopyEpi{mom}, stream);
   if (z_dtype == FRL_F32)
     FRL_LAUNCH(leakage_finalise_kernel<float>, dim3(1), dim3(256), 0, stream, (const float*)z, (const float*)mom, N, P, Dz, stats, cmat, centre);
   else
@@ -263,13 +243,7 @@ int frl_leakage_bwd(const void* z, int z_dtype, const float* cmat, const float* 
   int rc = lk_check(z, N, P, Dz, h_dtype, z_dtype);
   if (rc) return rc;
   if (cmat == nullptr || centre == nullptr || stats == nullptr || g == nullptr || dh == nullptr) return frl_fail(-2, "leakage_bwd: NULL argument");
-  if (z_dtype == FRL_F32) {
-    if (h_dtype == FRL_F32) rc = lk_launch_bwd<float, float>(z, cmat, centre, stats, g, N, P, Dz, dh, stream);
-    else rc = lk_launch_bwd<float, bf16>(z, cmat, centre, stats, g, N, P, Dz, dh, stream);
-  } else {
-    if (h_dtype == FRL_F32) rc = lk_launch_bwd<bf16, float>(z, cmat, centre, stats, g, N, P, Dz, dh, stream);
-    else rc = lk_launch_bwd<bf16, bf16>(z, cmat, centre, stats, g, N, P, Dz, dh, stream);
-  }
+  FRL_BY_DTYPE(z_dtype, TZ, FRL_BY_DTYPE(h_dtype, TH, rc = lk_launch_bwd<TZ, TH>(z, cmat, centre, stats, g, N, P, Dz, dh, stream)));
   if (rc) return rc;
   return frl_check_launch("leakage_bwd");
 }

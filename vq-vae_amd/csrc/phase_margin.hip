@@ -15,10 +15,11 @@
 //     which the caller folds into d emb with frl_segment_sum_rows.
 // Mapping: an item (a pixel; a (pair, role)) is one wave, up to four items per workgroup, each with its rows staged in its own slice of
 // LDS at an odd pitch (lanes over t' read distinct banks) and, backward, a T x 33 block of per-pair coefficients.  Distances come from
-// exact differences with the compensated sum of squares of soft_neighborhood.hip.  Reduction order is fixed (lanes strided over the
+// exact differences with the compensated sum of squares of frl_loss.hpp.  Reduction order is fixed (lanes strided over the
 // pairs of an item, a butterfly inside the wave, items strided over one workgroup in f64): no float atomics, bit-reproducible.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
+#include "frl_loss.hpp"
 #include <math.h>
 
 #define PM_MAX_T 32                                               // rows per item (T, M)
@@ -29,25 +30,6 @@
 // torch's softplus (beta 1, threshold 20) and its derivative
 __device__ __forceinline__ float pm_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float pm_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
-// compensated float32 sum of squares of a - b (the product's rounding error from the fma, the additions' by two-sum)
-__device__ __forceinline__ float pm_sumsq(const float* __restrict__ a, const float* __restrict__ b, int W) {
-  float s = 0.f, lo = 0.f;
-  for (int c = 0; c < W; ++c) {
-    const float df = a[c] - b[c];
-    const float p = df * df, pe = fmaf(df, df, -p);
-    const float n = s + p, bp = n - s;
-    lo += ((s - (n - bp)) + (p - bp)) + pe;
-    s = n;
-  }
-  return s + lo;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // recovery discrimination: wave = pixel.  FWD writes partial [N][2] = sum of softplus, pair count.  BWD writes grad [N][T][D], every row.
@@ -92,7 +74,7 @@ __global__ __launch_bounds__(256) void pm_recovery_kernel(const T* __restrict__ 
       for (int e = lane; e < Tn * Tn; e += 64) {
         const int tl = e / Tn, th = e - tl * Tn;
         if (((lom >> tl) & 1u) && ((him >> th) & 1u)) {
-          const float d = sqrtf(fmaxf(pm_sumsq(A + tl * pitch, A + th * pitch, D), 1e-12f));
+          const float d = sqrtf(fmaxf(sumsq_diff(A + tl * pitch, A + th * pitch, D), 1e-12f));
           s += pm_softplus(margin - d);
           cnt += 1;
         }
@@ -106,7 +88,7 @@ __global__ __launch_bounds__(256) void pm_recovery_kernel(const T* __restrict__ 
         const int tl = e / Tn, th = e - tl * Tn;
         float h = 0.f;
         if (((lom >> tl) & 1u) && ((him >> th) & 1u)) {
-          const float ss = pm_sumsq(A + tl * pitch, A + th * pitch, D);
+          const float ss = sumsq_diff(A + tl * pitch, A + th * pitch, D);
           if (ss > 1e-12f) {
             const float d = sqrtf(ss);
             h = sc * pm_sigmoid(margin - d) / d;
@@ -137,17 +119,9 @@ __global__ __launch_bounds__(1024) void pm_recovery_reduce_kernel(const float* _
     const float cnt = partial[2 * n + 1];
     if (cnt > 0.f) { s[0] += (double)partial[2 * n]; s[1] += (double)cnt; s[2] += 1.0; }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double v = wave_sum_d(s[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
+  block_sum_d<3, 16>(s, red);
   if (threadIdx.x == 0) {
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int w = 0; w < 16; ++w)
-      for (int k = 0; k < 3; ++k) v[k] += red[w][k];
+    const double* v = red[0];
     const float loss = v[1] > 0.0 ? (float)(v[0] / v[1]) : 0.f;
     out2[0] = loss;
     out2[1] = (float)v[1];
@@ -268,7 +242,7 @@ __global__ __launch_bounds__(256) void pm_spread_gathered_kernel(const T* __rest
     if (active)
       for (int e = lane; e < K * K; e += 64) {
         const int t = e / K, u = e - t * K;
-        if (t != u) s += sqrtf(pm_sumsq(A + t * pitch, A + u * pitch, D));
+        if (t != u) s += sqrtf(sumsq_diff(A + t * pitch, A + u * pitch, D));
       }
     s = wave_sum(s);
     if (inside && lane == 0) {
@@ -281,7 +255,7 @@ __global__ __launch_bounds__(256) void pm_spread_gathered_kernel(const T* __rest
         const int t = e / K, u = e - t * K;
         float h = 0.f;
         if (t != u) {
-          const float d = sqrtf(pm_sumsq(A + t * pitch, A + u * pitch, D));
+          const float d = sqrtf(sumsq_diff(A + t * pitch, A + u * pitch, D));
           h = d > 0.f ? 1.f / d : 0.f;
         }
         H[t * PM_HP + u] = h;
@@ -322,19 +296,7 @@ __global__ __launch_bounds__(1024) void pm_spread_reduce_kernel(const float* __r
     s[5] += (double)ps[1];
     s[6] += (double)fabsf(r);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const double v = wave_sum_d(s[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    double v = 0.0;
-    for (int w = 0; w < 16; ++w) v += red[w][threadIdx.x];
-    red[0][threadIdx.x] = v;
-  }
-  __syncthreads();
+  block_sum_d<7, 16>(s, red);
   if (threadIdx.x == 0) {
     const float loss = (float)(red[0][0] / (double)B);
     out2[0] = loss;
@@ -350,13 +312,6 @@ static int pm_items_per_block(int rows, int D, bool bwd, size_t* item_bytes) {
   *item_bytes = ((size_t)rows * (D | 1) + (bwd ? (size_t)rows * PM_HP : 0)) * sizeof(float);
   int ipb = (int)(PM_LDS_BUDGET / *item_bytes);
   return ipb > 4 ? 4 : (ipb < 1 ? 1 : ipb);
-}
-
-static unsigned pm_grid(int64_t work, int per_block) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (unsigned)g;
 }
 
 static int pm_check_recovery(int64_t N, int T, int D, int dtype) {
@@ -404,10 +359,8 @@ int frl_recovery_disc_fwd(const void* z, int dtype, const float* ysfc, int64_t N
   int rc = pm_check_recovery(N, T, D, dtype);
   if (rc) return rc;
   if (!z || !ysfc || !partial || !out2 || !stats) return frl_fail(-2, "recovery_disc_fwd: NULL argument");
-  if (dtype == FRL_F32)
-    pm_launch_recovery<float, false>(z, ysfc, N, T, D, margin, low_ysfc_max, high_ysfc_min, partial, nullptr, nullptr, nullptr, stream);
-  else
-    pm_launch_recovery<bf16, false>(z, ysfc, N, T, D, margin, low_ysfc_max, high_ysfc_min, partial, nullptr, nullptr, nullptr, stream);
+  FRL_BY_DTYPE(dtype, Tz,
+               pm_launch_recovery<Tz, false>(z, ysfc, N, T, D, margin, low_ysfc_max, high_ysfc_min, partial, nullptr, nullptr, nullptr, stream));
   FRL_LAUNCH(pm_recovery_reduce_kernel, dim3(1), dim3(1024), 0, stream, (const float*)partial, N, out2, stats);
   return frl_check_launch("recovery_disc_fwd");
 }
@@ -418,10 +371,7 @@ int frl_recovery_disc_bwd(const void* z, int dtype, const float* ysfc, int64_t N
   int rc = pm_check_recovery(N, T, D, dtype);
   if (rc) return rc;
   if (!z || !ysfc || !out2 || !gup || !grad) return frl_fail(-2, "recovery_disc_bwd: NULL argument");
-  if (dtype == FRL_F32)
-    pm_launch_recovery<float, true>(z, ysfc, N, T, D, margin, low_ysfc_max, high_ysfc_min, nullptr, out2, gup, grad, stream);
-  else
-    pm_launch_recovery<bf16, true>(z, ysfc, N, T, D, margin, low_ysfc_max, high_ysfc_min, nullptr, out2, gup, grad, stream);
+  FRL_BY_DTYPE(dtype, Tz, pm_launch_recovery<Tz, true>(z, ysfc, N, T, D, margin, low_ysfc_max, high_ysfc_min, nullptr, out2, gup, grad, stream));
   return frl_check_launch("recovery_disc_bwd");
 }
 
@@ -442,7 +392,7 @@ int frl_spread_rank_bwd(const unsigned char* mask, const float* pairstat, const 
   if (B < 1 || M < 1 || B > 0x3fffffff) return frl_fail(-2, "spread_rank_bwd: needs 1 <= B < 2^30 pairs and M >= 1");
   if (!mask || !pairstat || !ref_diff || !gup || !grad_i || !grad_j) return frl_fail(-2, "spread_rank_bwd: NULL argument");
   const int64_t mm = (int64_t)M * M;
-  FRL_LAUNCH(pm_spread_matrix_bwd_kernel, dim3(pm_grid(B * mm, 256)), dim3(256), 0, stream, mask, pairstat, ref_diff, gup, B, mm, margin, delta,
+  FRL_LAUNCH(pm_spread_matrix_bwd_kernel, dim3(frl_grid(B * mm, 256, 4096)), dim3(256), 0, stream, mask, pairstat, ref_diff, gup, B, mm, margin, delta,
              grad_i, grad_j);
   return frl_check_launch("spread_rank_bwd");
 }
@@ -456,10 +406,8 @@ int frl_spread_rank_gathered_fwd(const void* emb, int D, int emb_dtype, const in
   if (rc) return rc;
   if (!emb || !rows_i || !rows_j || !lengths || !ref_diff || !pairstat || !out2 || !stats)
     return frl_fail(-2, "spread_rank_gathered_fwd: NULL argument");
-  if (emb_dtype == FRL_F32)
-    pm_launch_spread<float, false>(emb, D, rows_i, rows_j, lengths, ref_diff, B, M, margin, delta, pairstat, nullptr, nullptr, stream);
-  else
-    pm_launch_spread<bf16, false>(emb, D, rows_i, rows_j, lengths, ref_diff, B, M, margin, delta, pairstat, nullptr, nullptr, stream);
+  FRL_BY_DTYPE(emb_dtype, T,
+               pm_launch_spread<T, false>(emb, D, rows_i, rows_j, lengths, ref_diff, B, M, margin, delta, pairstat, nullptr, nullptr, stream));
   FRL_LAUNCH(pm_spread_reduce_kernel, dim3(1), dim3(1024), 0, stream, (const float*)pairstat, ref_diff, B, margin, delta, out2, stats);
   return frl_check_launch("spread_rank_gathered_fwd");
 }
@@ -472,12 +420,9 @@ int frl_spread_rank_gathered_bwd(const void* emb, int D, int emb_dtype, const in
   if (rc) return rc;
   if (!emb || !rows_i || !rows_j || !lengths || !ref_diff || !pairstat || !gup || !grad_rows)
     return frl_fail(-2, "spread_rank_gathered_bwd: NULL argument");
-  if (emb_dtype == FRL_F32)
-    pm_launch_spread<float, true>(emb, D, rows_i, rows_j, lengths, ref_diff, B, M, margin, delta, const_cast<float*>(pairstat), gup, grad_rows,
-                                  stream);
-  else
-    pm_launch_spread<bf16, true>(emb, D, rows_i, rows_j, lengths, ref_diff, B, M, margin, delta, const_cast<float*>(pairstat), gup, grad_rows,
-                                 stream);
+  FRL_BY_DTYPE(emb_dtype, T,
+               pm_launch_spread<T, true>(emb, D, rows_i, rows_j, lengths, ref_diff, B, M, margin, delta, const_cast<float*>(pairstat), gup,
+                                         grad_rows, stream));
   return frl_check_launch("spread_rank_gathered_bwd");
 }
 

@@ -18,6 +18,7 @@
 // no float atomics, loss and gradients are bit-reproducible.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
+#include "frl_loss.hpp"
 #include <math.h>
 
 #define SN_MAX_M 32                                               // gathered form: positions per pair
@@ -150,19 +151,7 @@ __global__ __launch_bounds__(1024) void sn_reduce_kernel(const float* __restrict
       s[6] += (double)ps[SN_ENT_Q];
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const double v = wave_sum_d(s[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    double v = 0.0;
-    for (int w = 0; w < 16; ++w) v += red[w][threadIdx.x];
-    red[0][threadIdx.x] = v;
-  }
-  __syncthreads();
+  block_sum_d<7, 16>(s, red);
   if (threadIdx.x == 0) {
     const double sw = red[0][1];
     const float loss = sw > 0.0 ? (float)(red[0][0] / sw) : 0.f;
@@ -193,19 +182,7 @@ __device__ __forceinline__ void sn_stage(float* __restrict__ A, float* __restric
 __device__ __forceinline__ void sn_dist(float* __restrict__ dm, const float* __restrict__ A, const float* __restrict__ Bm, int pitch, int W, int K) {
   for (int e = threadIdx.x; e < K * K; e += 256) {
     const int t = e / K, u = e - t * K;
-    const float* a = A + t * pitch;
-    const float* b = Bm + u * pitch;
-    // compensated float32 sum of the squares (the product's own rounding error from the fma, the additions' by two-sum): a plain running
-    // sum over 256 columns loses 3e-7 of d, which a logit of -d / tau = -45 turns into more than the loss bound allows
-    float s = 0.f, lo = 0.f;
-    for (int c = 0; c < W; ++c) {
-      const float df = a[c] - b[c];
-      const float p = df * df, pe = fmaf(df, df, -p);
-      const float n = s + p, bp = n - s;
-      lo += ((s - (n - bp)) + (p - bp)) + pe;
-      s = n;
-    }
-    dm[t * SN_DP + u] = sqrtf(s + lo);
+    dm[t * SN_DP + u] = sqrtf(sumsq_diff(A + t * pitch, Bm + u * pitch, W));
   }
 }
 
@@ -287,13 +264,6 @@ __global__ __launch_bounds__(256) void sn_gathered_kernel(const float* __restric
   }
 }
 
-static unsigned sn_grid(int64_t work, int per_block) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
 static int sn_check_matrix(int64_t B, int M, float itr, float itl, int min_valid) {
   if (B < 1 || M < 1 || B > 0x7fffffff) return frl_fail(-2, "soft_nbr: needs 1 <= B < 2^31 pairs and M >= 1");
   if (!(itr > 0.f) || !(itl > 0.f)) return frl_fail(-2, "soft_nbr: temperatures must be positive");
@@ -347,7 +317,7 @@ int frl_soft_nbr_bwd(const float* coef, const float* pairstat, const float* weig
   if (B < 1 || M < 1) return frl_fail(-2, "soft_nbr_bwd: needs B >= 1 and M >= 1");
   if (!coef || !pairstat || !out2 || !gup || !grad) return frl_fail(-2, "soft_nbr_bwd: NULL argument");
   const int64_t mm = (int64_t)M * M;
-  FRL_LAUNCH(sn_matrix_bwd_kernel, dim3(sn_grid(B * mm, 256)), dim3(256), 0, stream, coef, pairstat, weights, out2, gup, B * mm, mm, grad);
+  FRL_LAUNCH(sn_matrix_bwd_kernel, dim3(frl_grid(B * mm, 256, 4096)), dim3(256), 0, stream, coef, pairstat, weights, out2, gup, B * mm, mm, grad);
   return frl_check_launch("soft_nbr_bwd");
 }
 
@@ -361,12 +331,10 @@ int frl_soft_nbr_gathered_fwd(const float* ref, int C, const void* emb, int D, i
   if (rc) return rc;
   if (!ref || !emb || !ref_rows_a || !ref_rows_b || !emb_rows_a || !emb_rows_b || !lengths || !pairstat || !out2 || !stats)
     return frl_fail(-2, "soft_nbr_gathered_fwd: NULL argument");
-  if (emb_dtype == FRL_F32)
-    rc = sn_launch_gathered<float, false>(ref, C, emb, D, ref_rows_a, ref_rows_b, emb_rows_a, emb_rows_b, lengths, weights, B, M, exclude_diagonal,
-                                          inv_tau_ref, inv_tau_learned, min_valid, pairstat, nullptr, nullptr, nullptr, stream);
-  else
-    rc = sn_launch_gathered<bf16, false>(ref, C, emb, D, ref_rows_a, ref_rows_b, emb_rows_a, emb_rows_b, lengths, weights, B, M, exclude_diagonal,
-                                         inv_tau_ref, inv_tau_learned, min_valid, pairstat, nullptr, nullptr, nullptr, stream);
+  FRL_BY_DTYPE(emb_dtype, T,
+               rc = sn_launch_gathered<T, false>(ref, C, emb, D, ref_rows_a, ref_rows_b, emb_rows_a, emb_rows_b, lengths, weights, B, M,
+                                                 exclude_diagonal, inv_tau_ref, inv_tau_learned, min_valid, pairstat, nullptr, nullptr, nullptr,
+                                                 stream));
   if (rc) return rc;
   FRL_LAUNCH(sn_reduce_kernel, dim3(1), dim3(1024), 0, stream, (const float*)pairstat, weights, B, out2, stats);
   return frl_check_launch("soft_nbr_gathered_fwd");
@@ -381,12 +349,10 @@ int frl_soft_nbr_gathered_bwd(const float* ref, int C, const void* emb, int D, i
   if (rc) return rc;
   if (!ref || !emb || !ref_rows_a || !ref_rows_b || !emb_rows_a || !emb_rows_b || !lengths || !pairstat || !out2 || !gup || !grad_rows)
     return frl_fail(-2, "soft_nbr_gathered_bwd: NULL argument");
-  if (emb_dtype == FRL_F32)
-    rc = sn_launch_gathered<float, true>(ref, C, emb, D, ref_rows_a, ref_rows_b, emb_rows_a, emb_rows_b, lengths, weights, B, M, exclude_diagonal,
-                                         inv_tau_ref, inv_tau_learned, min_valid, const_cast<float*>(pairstat), out2, gup, grad_rows, stream);
-  else
-    rc = sn_launch_gathered<bf16, true>(ref, C, emb, D, ref_rows_a, ref_rows_b, emb_rows_a, emb_rows_b, lengths, weights, B, M, exclude_diagonal,
-                                        inv_tau_ref, inv_tau_learned, min_valid, const_cast<float*>(pairstat), out2, gup, grad_rows, stream);
+  FRL_BY_DTYPE(emb_dtype, T,
+               rc = sn_launch_gathered<T, true>(ref, C, emb, D, ref_rows_a, ref_rows_b, emb_rows_a, emb_rows_b, lengths, weights, B, M,
+                                                exclude_diagonal, inv_tau_ref, inv_tau_learned, min_valid, const_cast<float*>(pairstat), out2,
+                                                gup, grad_rows, stream));
   if (rc) return rc;
   return frl_check_launch("soft_nbr_gathered_bwd");
 }

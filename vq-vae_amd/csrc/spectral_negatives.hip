@@ -15,12 +15,13 @@
 // caller's flag word, and no address outside the arrays is ever formed.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
+#include "frl_loss.hpp"
 #include <math.h>
 
-#define SN_BLOCK 256
-#define SN_GROUPS (SN_BLOCK / 16)
-#define SN_GRID_MAX 2048
-#define SN_MAX_WIDTH 256
+#define SPN_BLOCK 256
+#define SPN_GROUPS (SPN_BLOCK / 16)
+#define SPN_GRID_MAX 2048
+#define SPN_MAX_WIDTH 256
 
 // sum_c (a[c] - b[c])^2 over one 16-lane group; every lane of the group returns the sum
 template <bool VEC>
@@ -37,16 +38,14 @@ __device__ __forceinline__ float group16_sqdist(const float* __restrict__ a, con
   } else {
     for (int j = l; j < C; j += 16) { const float df = a[j] - b[j]; s = fmaf(df, df, s); }
   }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  return s;
+  return group16_sum(s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // negative q -> (i, j), |spec[i] - spec[j]|, weight.  flag bits: 1 a negative draw (taken as 0), 2 patch bounds that are not
 // 0 <= offsets[p] < offsets[p + 1] <= N (clamped to a non-empty range inside the array)
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t sn_pick(const int32_t* __restrict__ offsets, int p, int draw, int64_t N, int& bad) {
+__device__ __forceinline__ int64_t spn_pick(const int32_t* __restrict__ offsets, int p, int draw, int64_t N, int& bad) {
   int64_t lo = offsets[p], hi = offsets[p + 1];
   if (lo < 0 || hi > N || hi <= lo) {
     bad |= 2;
@@ -59,19 +58,19 @@ __device__ __forceinline__ int64_t sn_pick(const int32_t* __restrict__ offsets, 
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(SN_BLOCK) void spectral_negatives_kernel(const float* __restrict__ spec, int64_t N, int C,
+__global__ __launch_bounds__(SPN_BLOCK) void spectral_negatives_kernel(const float* __restrict__ spec, int64_t N, int C,
                                                                       const int32_t* __restrict__ offsets, int S, int n_per,
                                                                       const int32_t* __restrict__ draws, int64_t Q, float tau, float min_w,
                                                                       int64_t* __restrict__ pairs, float* __restrict__ dist,
                                                                       float* __restrict__ weights, int* __restrict__ flag) {
   const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
   int bad = 0;
-  for (int64_t q = (int64_t)blockIdx.x * SN_GROUPS + g; q < Q; q += (int64_t)gridDim.x * SN_GROUPS) {
+  for (int64_t q = (int64_t)blockIdx.x * SPN_GROUPS + g; q < Q; q += (int64_t)gridDim.x * SPN_GROUPS) {
     const uint32_t b = (uint32_t)q / (uint32_t)n_per;                // Q < 2^31: 32-bit divisions
     const int pi = (int)(b / (uint32_t)(S - 1)), r = (int)(b % (uint32_t)(S - 1));
     const int pj = r + (r >= pi ? 1 : 0);
-    const int64_t i = sn_pick(offsets, pi, draws[2 * q], N, bad);
-    const int64_t j = sn_pick(offsets, pj, draws[2 * q + 1], N, bad);
+    const int64_t i = spn_pick(offsets, pi, draws[2 * q], N, bad);
+    const int64_t j = spn_pick(offsets, pj, draws[2 * q + 1], N, bad);
     const float d = sqrtf(group16_sqdist<VEC>(spec + i * C, spec + j * C, C, l));
     if (l == 0) {
       const float w = 1.f - expf(-d / tau);
@@ -95,14 +94,14 @@ __device__ __forceinline__ int64_t ps_row(int64_t v, int64_t N, int& bad) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(SN_BLOCK) void pair_sims_kernel(const float* __restrict__ emb, int64_t N, int D, const int64_t* __restrict__ pairs,
+__global__ __launch_bounds__(SPN_BLOCK) void pair_sims_kernel(const float* __restrict__ emb, int64_t N, int D, const int64_t* __restrict__ pairs,
                                                              int64_t T, float* __restrict__ sims, double* __restrict__ partial,
                                                              int* __restrict__ flag) {
-  __shared__ double red[SN_GROUPS][2];
+  __shared__ double red[SPN_GROUPS][2];
   const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
   int bad = 0;
   double s1 = 0.0, s2 = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * SN_GROUPS + g; t < T; t += (int64_t)gridDim.x * SN_GROUPS) {
+  for (int64_t t = (int64_t)blockIdx.x * SPN_GROUPS + g; t < T; t += (int64_t)gridDim.x * SPN_GROUPS) {
     const int64_t a = ps_row(pairs[2 * t], N, bad), b = ps_row(pairs[2 * t + 1], N, bad);
     const float sim = -group16_sqdist<VEC>(emb + a * D, emb + b * D, D, l) / (float)D;
     if (l == 0) sims[t] = sim;
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(SN_BLOCK) void pair_sims_kernel(const float* __rest
   __syncthreads();
   if (threadIdx.x == 0) {
     double t1 = 0.0, t2 = 0.0;
-    for (int k = 0; k < SN_GROUPS; ++k) { t1 += red[k][0]; t2 += red[k][1]; }
+    for (int k = 0; k < SPN_GROUPS; ++k) { t1 += red[k][0]; t2 += red[k][1]; }
     partial[2 * blockIdx.x] = t1;
     partial[2 * blockIdx.x + 1] = t2;
   }
@@ -124,14 +123,14 @@ __global__ __launch_bounds__(SN_BLOCK) void pair_sims_kernel(const float* __rest
 // stats = (T, mean, unbiased standard deviation, 0) from the nb workgroup partials: one workgroup, fixed order.  The sims are float32
 // values, so a spread below 6e-8 |mean| is not resolved by the data itself; the cancellation in sum(x^2) - sum(x)^2 / T, 1e-16 mean^2 in
 // double, lies below that.
-__global__ __launch_bounds__(SN_BLOCK) void pair_sims_finish_kernel(const double* __restrict__ partial, int nb, int64_t T, double* __restrict__ stats) {
-  __shared__ double red[SN_BLOCK][2];
+__global__ __launch_bounds__(SPN_BLOCK) void pair_sims_finish_kernel(const double* __restrict__ partial, int nb, int64_t T, double* __restrict__ stats) {
+  __shared__ double red[SPN_BLOCK][2];
   double t1 = 0.0, t2 = 0.0;
-  for (int i = threadIdx.x; i < nb; i += SN_BLOCK) { t1 += partial[2 * i]; t2 += partial[2 * i + 1]; }
+  for (int i = threadIdx.x; i < nb; i += SPN_BLOCK) { t1 += partial[2 * i]; t2 += partial[2 * i + 1]; }
   red[threadIdx.x][0] = t1;
   red[threadIdx.x][1] = t2;
   __syncthreads();
-  for (int o = SN_BLOCK / 2; o > 0; o >>= 1) {
+  for (int o = SPN_BLOCK / 2; o > 0; o >>= 1) {
     if (threadIdx.x < o) { red[threadIdx.x][0] += red[threadIdx.x + o][0]; red[threadIdx.x][1] += red[threadIdx.x + o][1]; }
     __syncthreads();
   }
@@ -145,20 +144,15 @@ __global__ __launch_bounds__(SN_BLOCK) void pair_sims_finish_kernel(const double
   }
 }
 
-static unsigned sn_grid(int64_t work) {
-  int64_t g = (work + SN_GROUPS - 1) / SN_GROUPS;
-  if (g > SN_GRID_MAX) g = SN_GRID_MAX;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
+static unsigned spn_grid(int64_t work) { return frl_grid(work, SPN_GROUPS, SPN_GRID_MAX); }
 
-static bool sn_vec_ok(const void* rows, int width) { return (width & 3) == 0 && ((uintptr_t)rows & 15) == 0; }
+static bool spn_vec_ok(const void* rows, int width) { return (width & 3) == 0 && ((uintptr_t)rows & 15) == 0; }
 
 extern "C" {
 
 int frl_spectral_negatives(const float* spec, int64_t N, int C, const int32_t* offsets, int S, int n_per, const int32_t* draws, int64_t Q,
                            float tau, float min_w, int64_t* pairs, float* dist, float* weights, int32_t* index_flag, hipStream_t stream) {
-  if (C < 1 || C > SN_MAX_WIDTH) return frl_fail(-2, "spectral_negatives: C must be in 1..256");
+  if (C < 1 || C > SPN_MAX_WIDTH) return frl_fail(-2, "spectral_negatives: C must be in 1..256");
   if (Q < 0) return frl_fail(-2, "spectral_negatives: Q < 0");
   if (Q == 0) return 0;
   if (S < 2) return frl_fail(-2, "spectral_negatives: negatives need at least two patches");
@@ -169,20 +163,20 @@ int frl_spectral_negatives(const float* spec, int64_t N, int C, const int32_t* o
   if (spec == nullptr || offsets == nullptr || draws == nullptr || pairs == nullptr || dist == nullptr || weights == nullptr)
     return frl_fail(-1, "spectral_negatives: null pointer");
   int* flag = reinterpret_cast<int*>(index_flag);
-  if (sn_vec_ok(spec, C))
-    FRL_LAUNCH((spectral_negatives_kernel<true>), dim3(sn_grid(Q)), dim3(SN_BLOCK), 0, stream, spec, N, C, offsets, S, n_per, draws, Q, tau, min_w,
+  if (spn_vec_ok(spec, C))
+    FRL_LAUNCH((spectral_negatives_kernel<true>), dim3(spn_grid(Q)), dim3(SPN_BLOCK), 0, stream, spec, N, C, offsets, S, n_per, draws, Q, tau, min_w,
                pairs, dist, weights, flag);
   else
-    FRL_LAUNCH((spectral_negatives_kernel<false>), dim3(sn_grid(Q)), dim3(SN_BLOCK), 0, stream, spec, N, C, offsets, S, n_per, draws, Q, tau, min_w,
+    FRL_LAUNCH((spectral_negatives_kernel<false>), dim3(spn_grid(Q)), dim3(SPN_BLOCK), 0, stream, spec, N, C, offsets, S, n_per, draws, Q, tau, min_w,
                pairs, dist, weights, flag);
   return frl_check_launch("spectral_negatives");
 }
 
-size_t frl_pair_sims_workspace_bytes(int64_t T) { return T > 0 ? (size_t)sn_grid(T) * 2 * sizeof(double) : 0; }
+size_t frl_pair_sims_workspace_bytes(int64_t T) { return T > 0 ? (size_t)spn_grid(T) * 2 * sizeof(double) : 0; }
 
 int frl_pair_sims(const float* emb, int64_t N, int D, const int64_t* pairs, int64_t T, float* sims, double* stats, int32_t* index_flag, void* ws,
                   size_t ws_bytes, hipStream_t stream) {
-  if (D < 1 || D > SN_MAX_WIDTH) return frl_fail(-2, "pair_sims: D must be in 1..256");
+  if (D < 1 || D > SPN_MAX_WIDTH) return frl_fail(-2, "pair_sims: D must be in 1..256");
   if (T < 0) return frl_fail(-2, "pair_sims: T < 0");
   if (T == 0) return 0;
   if (N < 1) return frl_fail(-2, "pair_sims: pairs over an empty embedding matrix");
@@ -191,13 +185,13 @@ int frl_pair_sims(const float* emb, int64_t N, int D, const int64_t* pairs, int6
     return frl_fail(-3, "pair_sims: statistics need an 8-byte aligned workspace of frl_pair_sims_workspace_bytes(T)");
   double* partial = stats != nullptr ? reinterpret_cast<double*>(ws) : nullptr;
   int* flag = reinterpret_cast<int*>(index_flag);
-  const unsigned nb = sn_grid(T);
-  if (sn_vec_ok(emb, D))
-    FRL_LAUNCH((pair_sims_kernel<true>), dim3(nb), dim3(SN_BLOCK), 0, stream, emb, N, D, pairs, T, sims, partial, flag);
+  const unsigned nb = spn_grid(T);
+  if (spn_vec_ok(emb, D))
+    FRL_LAUNCH((pair_sims_kernel<true>), dim3(nb), dim3(SPN_BLOCK), 0, stream, emb, N, D, pairs, T, sims, partial, flag);
   else
-    FRL_LAUNCH((pair_sims_kernel<false>), dim3(nb), dim3(SN_BLOCK), 0, stream, emb, N, D, pairs, T, sims, partial, flag);
+    FRL_LAUNCH((pair_sims_kernel<false>), dim3(nb), dim3(SPN_BLOCK), 0, stream, emb, N, D, pairs, T, sims, partial, flag);
   if (stats != nullptr)
-    FRL_LAUNCH(pair_sims_finish_kernel, dim3(1), dim3(SN_BLOCK), 0, stream, (const double*)partial, (int)nb, T, stats);
+    FRL_LAUNCH(pair_sims_finish_kernel, dim3(1), dim3(SPN_BLOCK), 0, stream, (const double*)partial, (int)nb, T, stats);
   return frl_check_launch("pair_sims");
 }
 

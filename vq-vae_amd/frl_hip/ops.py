@@ -194,6 +194,19 @@ def _f32(t: Optional[torch.Tensor], name: str):
     return t
 
 
+def _chk_f32_on(op: str, anchor: str, device, *operands):
+    """Each (tensor, shape, name): a contiguous float32 tensor of exactly that shape on `device`, the device of the operand called `anchor`."""
+    for t, shape, name in operands:
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{op}: {name} must be a contiguous float32 {shape} tensor on the device of {anchor}")
+
+
+def _pair_outputs(b: int, width: int, device):
+    """pairstat f32 [B, width], out2 f32 [2], stats f64 [8] of the pair losses (soft neighbourhood, spread ranking)."""
+    return (torch.empty(b, width, dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
+            torch.empty(8, dtype=torch.float64, device=device))
+
+
 _DEFER = {"on": False, "keep": [], "dest": {}, "drop": set()}
 
 
@@ -1713,9 +1726,7 @@ def vicreg_bwd(x: torch.Tensor, cov: torch.Tensor, centre: torch.Tensor, g3: tor
     """dx [N, D] in the dtype of x for the upstream gradients g3 f32 [3] of (total, variance_loss, covariance_loss), read on the device."""
     _chk_vicreg(x, "vicreg_bwd")
     n, d = x.shape
-    for t, shape, name in ((cov, (d, d), "cov"), (centre, (2, d), "centre"), (g3, (3,), "g3")):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"vicreg_bwd: {name} must be a contiguous float32 {shape} tensor on the device of x")
+    _chk_f32_on("vicreg_bwd", "x", x.device, (cov, (d, d), "cov"), (centre, (2, d), "centre"), (g3, (3,), "g3"))
     dx = torch.empty_like(x)
     check(_lib.load().frl_vicreg_bwd(_p(x), _p(cov), _p(centre), _p(g3), n, d, _dt(x), float(variance_weight), float(covariance_weight),
                                      float(variance_target), float(eps), _p(dx), _stream()), "frl_vicreg_bwd")
@@ -1826,9 +1837,7 @@ def leakage_bwd(z: torch.Tensor, cmat: torch.Tensor, centre: torch.Tensor, stats
     dh = torch.empty((n, p), dtype=dtype, device=z.device)
     chk_leakage(dh, z, "leakage_bwd")
     _chk_leakage_dev(dh, z, "leakage_bwd")
-    for t, shape, name in ((cmat, (p, dz), "cmat"), (centre, (2, dz), "centre"), (stats, (2,), "stats"), (g, (1,), "g")):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != z.device:
-            raise ValueError(f"leakage_bwd: {name} must be a contiguous float32 {shape} tensor on the device of z")
+    _chk_f32_on("leakage_bwd", "z", z.device, (cmat, (p, dz), "cmat"), (centre, (2, dz), "centre"), (stats, (2,), "stats"), (g, (1,), "g"))
     check(_lib.load().frl_leakage_bwd(_p(z), _dt(z), _p(cmat), _p(centre), _p(stats), _p(g), n, p, dz, _p(dh), _dt(dh), _stream()),
           "frl_leakage_bwd")
     return dh
@@ -1855,11 +1864,6 @@ def _soft_nbr_weights(weights: Optional[torch.Tensor], b: int, device, name: str
     return weights
 
 
-def _soft_nbr_outputs(b: int, device):
-    return (torch.empty(b, 6, dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
-            torch.empty(8, dtype=torch.float64, device=device))
-
-
 @_timed("soft_nbr_fwd")
 def soft_nbr_fwd(d_reference: torch.Tensor, d_learned: torch.Tensor, mask: torch.Tensor, weights: Optional[torch.Tensor] = None,
                  tau_ref: float = 1.0, tau_learned: float = 1.0, min_valid_per_row: int = 2, want_coef: bool = True):
@@ -1876,7 +1880,7 @@ def soft_nbr_fwd(d_reference: torch.Tensor, d_learned: torch.Tensor, mask: torch
             raise ValueError(f"soft_nbr_fwd: {name} must be a contiguous {dt} {tuple(d_reference.shape)} tensor on {d_reference.device}")
     b, m, _ = d_reference.shape
     weights = _soft_nbr_weights(weights, b, d_reference.device, "soft_nbr_fwd")
-    pairstat, out2, stats = _soft_nbr_outputs(b, d_reference.device)
+    pairstat, out2, stats = _pair_outputs(b, 6, d_reference.device)
     coef = torch.empty_like(d_learned) if want_coef else None
     check(_lib.load().frl_soft_nbr_fwd(_p(d_reference), _p(d_learned), _p(mask), _p(weights), b, m, 1.0 / float(tau_ref), 1.0 / float(tau_learned),
                                        int(min_valid_per_row), _p(pairstat), _p(coef), _p(out2), _p(stats), _stream()), "frl_soft_nbr_fwd")
@@ -1889,9 +1893,7 @@ def soft_nbr_bwd(coef: torch.Tensor, pairstat: torch.Tensor, weights: Optional[t
     if not coef.is_cuda:
         raise _lib.FrlHipError("soft_nbr_bwd: tensors must live on the GPU (no CPU fallback)")
     b, m, _ = coef.shape
-    for t, shape, name in ((coef, (b, m, m), "coef"), (pairstat, (b, 6), "pairstat"), (out2, (2,), "out2"), (g, (1,), "g")):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != coef.device:
-            raise ValueError(f"soft_nbr_bwd: {name} must be a contiguous float32 {shape} tensor on the device of coef")
+    _chk_f32_on("soft_nbr_bwd", "coef", coef.device, (coef, (b, m, m), "coef"), (pairstat, (b, 6), "pairstat"), (out2, (2,), "out2"), (g, (1,), "g"))
     weights = _soft_nbr_weights(weights, b, coef.device, "soft_nbr_bwd")
     grad = torch.empty_like(coef)
     check(_lib.load().frl_soft_nbr_bwd(_p(coef), _p(pairstat), _p(weights), _p(out2), _p(g), b, m, _p(grad), _stream()), "frl_soft_nbr_bwd")
@@ -1932,7 +1934,7 @@ def soft_nbr_gathered_fwd(ref: torch.Tensor, emb: torch.Tensor, rows: torch.Tens
     _chk_soft_nbr("soft_nbr_gathered_fwd", tau_ref, tau_learned, min_valid_per_row)
     b, m, rows = _chk_soft_nbr_gathered("soft_nbr_gathered_fwd", ref, emb, rows, lengths, checked)
     weights = _soft_nbr_weights(weights, b, ref.device, "soft_nbr_gathered_fwd")
-    pairstat, out2, stats = _soft_nbr_outputs(b, ref.device)
+    pairstat, out2, stats = _pair_outputs(b, 6, ref.device)
     check(_lib.load().frl_soft_nbr_gathered_fwd(_p(ref), ref.shape[1], _p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(rows[2]),
                                                 _p(rows[3]), _p(lengths), _p(weights), b, m, int(bool(exclude_diagonal)), 1.0 / float(tau_ref),
                                                 1.0 / float(tau_learned), int(min_valid_per_row), _p(pairstat), _p(out2), _p(stats), _stream()),
@@ -1948,9 +1950,7 @@ def soft_nbr_gathered_bwd(ref: torch.Tensor, emb: torch.Tensor, rows: torch.Tens
     into d emb with segment_sum_rows.  g: float32 [1] on the device."""
     _chk_soft_nbr("soft_nbr_gathered_bwd", tau_ref, tau_learned, min_valid_per_row)
     b, m, rows = _chk_soft_nbr_gathered("soft_nbr_gathered_bwd", ref, emb, rows, lengths, checked)
-    for t, shape, name in ((pairstat, (b, 6), "pairstat"), (out2, (2,), "out2"), (g, (1,), "g")):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != ref.device:
-            raise ValueError(f"soft_nbr_gathered_bwd: {name} must be a contiguous float32 {shape} tensor on the device of ref")
+    _chk_f32_on("soft_nbr_gathered_bwd", "ref", ref.device, (pairstat, (b, 6), "pairstat"), (out2, (2,), "out2"), (g, (1,), "g"))
     weights = _soft_nbr_weights(weights, b, ref.device, "soft_nbr_gathered_bwd")
     grows = torch.empty(2, b, m, emb.shape[1], dtype=torch.float32, device=ref.device)
     check(_lib.load().frl_soft_nbr_gathered_bwd(_p(ref), ref.shape[1], _p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(rows[2]),
@@ -2081,18 +2081,11 @@ def recovery_disc_bwd(z: torch.Tensor, ysfc: torch.Tensor, margin: float, low_ys
                       g: torch.Tensor) -> torch.Tensor:
     """d z [N, T, D] in z's dtype for the outputs of recovery_disc_fwd, every row written; g: float32 [1] on the device."""
     n, t, d = _chk_recovery_disc("recovery_disc_bwd", z, ysfc)
-    for x, shape, name in ((out2, (2,), "out2"), (g, (1,), "g")):
-        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != z.device:
-            raise ValueError(f"recovery_disc_bwd: {name} must be a contiguous float32 {shape} tensor on the device of z")
+    _chk_f32_on("recovery_disc_bwd", "z", z.device, (out2, (2,), "out2"), (g, (1,), "g"))
     grad = torch.empty_like(z)
     check(_lib.load().frl_recovery_disc_bwd(_p(z), _dt(z), _p(ysfc), n, t, d, float(margin), float(low_ysfc_max), float(high_ysfc_min),
                                             _p(out2), _p(g), _p(grad), _stream()), "frl_recovery_disc_bwd")
     return grad
-
-
-def _spread_rank_outputs(b: int, device):
-    return (torch.empty(b, 3, dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
-            torch.empty(8, dtype=torch.float64, device=device))
 
 
 def _chk_spread_ref_diff(name: str, ref_diff: torch.Tensor, b: int, device):
@@ -2126,7 +2119,7 @@ def spread_rank_fwd(d_i: torch.Tensor, d_j: torch.Tensor, mask: torch.Tensor, re
     """d_i, d_j [B, M, M] float32, mask [B, M, M] bool, ref_diff [B] float32 -> (out2 f32 [2] = loss, B; stats f64 [8] = loss, constrained i,
     constrained j, satisfied, sum spread_i, sum spread_j, sum |ref_diff|, B; pairstat f32 [B, 3] = spread_i, spread_j, n_b)."""
     b, m = _chk_spread_rank("spread_rank_fwd", mask, ref_diff, (d_i, d_j))
-    pairstat, out2, stats = _spread_rank_outputs(b, mask.device)
+    pairstat, out2, stats = _pair_outputs(b, 3, mask.device)
     check(_lib.load().frl_spread_rank_fwd(_p(d_i), _p(d_j), _p(mask), _p(ref_diff), b, m, float(margin), float(delta), _p(pairstat), _p(out2),
                                           _p(stats), _stream()), "frl_spread_rank_fwd")
     return out2, stats, pairstat
@@ -2136,9 +2129,7 @@ def spread_rank_fwd(d_i: torch.Tensor, d_j: torch.Tensor, mask: torch.Tensor, re
 def spread_rank_bwd(mask: torch.Tensor, pairstat: torch.Tensor, ref_diff: torch.Tensor, margin: float, delta: float, g: torch.Tensor):
     """(d loss / d d_i, d loss / d d_j) float32 [B, M, M] for the outputs of spread_rank_fwd; g: float32 [1] on the device."""
     b, m = _chk_spread_rank("spread_rank_bwd", mask, ref_diff, ())
-    for x, shape, name in ((pairstat, (b, 3), "pairstat"), (g, (1,), "g")):
-        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != mask.device:
-            raise ValueError(f"spread_rank_bwd: {name} must be a contiguous float32 {shape} tensor on the device of mask")
+    _chk_f32_on("spread_rank_bwd", "mask", mask.device, (pairstat, (b, 3), "pairstat"), (g, (1,), "g"))
     gi = torch.empty(b, m, m, dtype=torch.float32, device=mask.device)
     gj = torch.empty_like(gi)
     check(_lib.load().frl_spread_rank_bwd(_p(mask), _p(pairstat), _p(ref_diff), _p(g), b, m, float(margin), float(delta), _p(gi), _p(gj),
@@ -2179,7 +2170,7 @@ def spread_rank_gathered_fwd(emb: torch.Tensor, rows: torch.Tensor, lengths: tor
     """emb [R, D] float32 | bfloat16, rows [2, B, M] int64 (role i, role j), lengths [B] int64, ref_diff [B] float32 -> (out2, stats,
     pairstat as spread_rank_fwd, rows sanitised into [0, R)).  M <= 32, D <= 256."""
     b, m, rows = _chk_spread_rank_gathered("spread_rank_gathered_fwd", emb, rows, lengths, ref_diff, checked)
-    pairstat, out2, stats = _spread_rank_outputs(b, emb.device)
+    pairstat, out2, stats = _pair_outputs(b, 3, emb.device)
     check(_lib.load().frl_spread_rank_gathered_fwd(_p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(lengths), _p(ref_diff), b, m,
                                                    float(margin), float(delta), _p(pairstat), _p(out2), _p(stats), _stream()),
           "frl_spread_rank_gathered_fwd")
@@ -2192,9 +2183,7 @@ def spread_rank_gathered_bwd(emb: torch.Tensor, rows: torch.Tensor, lengths: tor
     """Gradient rows float32 [2, B, M, D] (role i, then role j) for the outputs of spread_rank_gathered_fwd; fold them into d emb with
     segment_sum_rows.  g: float32 [1] on the device."""
     b, m, rows = _chk_spread_rank_gathered("spread_rank_gathered_bwd", emb, rows, lengths, ref_diff, checked)
-    for x, shape, name in ((pairstat, (b, 3), "pairstat"), (g, (1,), "g")):
-        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != emb.device:
-            raise ValueError(f"spread_rank_gathered_bwd: {name} must be a contiguous float32 {shape} tensor on the device of emb")
+    _chk_f32_on("spread_rank_gathered_bwd", "emb", emb.device, (pairstat, (b, 3), "pairstat"), (g, (1,), "g"))
     grows = torch.empty(2, b, m, emb.shape[1], dtype=torch.float32, device=emb.device)
     check(_lib.load().frl_spread_rank_gathered_bwd(_p(emb), emb.shape[1], _dt(emb), _p(rows[0]), _p(rows[1]), _p(lengths), _p(ref_diff), b, m,
                                                    float(margin), float(delta), _p(pairstat), _p(g), _p(grows), _stream()),
