@@ -121,12 +121,20 @@ def test_vq_assign_bit_exact(dtype, N, K, d, ties):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("N,K,d,dup", [(66000, 512, 64, 2), (4096, 512, 64, 2), (3000, 64, 64, 64), (70000, 256, 32, 4), (2048, 1024, 64, 2)])
+@pytest.mark.parametrize("N,K,d,dup", [(66000, 512, 64, 2), (4096, 512, 64, 2), (3000, 64, 64, 64), (70000, 256, 32, 4), (2048, 1024, 64, 2),
+                                       # multi-chunk route with four duplicates: they fall into one lane's four accumulator rows, so the
+                                       # fixup kernel flushes with both pending slots taken (with dup = 2 it never does)
+                                       (2048, 1024, 64, 4),
+                                       # multi-chunk with K % 16 != 0 and d below the padded width: the channel guard of the shared row
+                                       # write and the scalar branch of the exact distance, from the fixup kernel
+                                       (1000, 1040, 12, 4)])
 def test_vq_assign_every_row_is_a_tie(dtype, N, K, d, dup):
     """Worst case of the exact re-evaluation: the codebook holds every vector `dup` times, so EVERY row ties between `dup` codes
     (dup = K: all codes identical) -- the first index must win everywhere.  Exercises the in-kernel list drain (far more parked rows
     than the list holds), the pending-candidate flush (more than two candidates per lane) and, for K = 1024, the multi-chunk path.
-    Also checks that a prepared codebook image gives the same result as the one-call entry point."""
+    Also checks that a prepared codebook image gives the same result as the one-call entry point.
+    (1000, 1040, 12, 4) also ends the flagged-row list of the multi-chunk route in a partial tile, so which rows meet in a tile of the
+    fixup kernel depends on timing: stats must not."""
     from frl_hip import ops
     dev = _dev()
     g = torch.Generator().manual_seed(N + K + dup)
