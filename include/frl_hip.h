@@ -784,6 +784,36 @@ int frl_probe_evaluate(const float* A, int Ta, int Da, const float* Bs, int Tb, 
                        int B, int T, int64_t P, const float* pivot, const float* Wc, const float* bc, int workgroups, double* E, int64_t* n,
                        float* pred, void* ws, size_t ws_bytes, frl_stream_t stream);
 
+/* ---- EVT-stratified diagnostics (csrc/strata.hip) ----------------------------------------------------------------------------------
+ * The grouped accumulation of frl/training/compare_gmm_evt.py, phase_evt_diagnostics.py and ysfc_evt_histograms.py.
+ * An observation is (b, t, p) with b < B, t < T, p < P (B T P < 2^31).  Its key is codes [B][P], int32 (codes_float = 0) or float32
+ * (codes_float = 1), looked up in vocab [G] (int32, strictly increasing, 1 <= G <= 4095).  A code is valid when it is finite and > 0; a
+ * valid float code is truncated towards zero (2^31 and above: INT_MAX).  mask (uint8 [B][Tm][P], Tm 1 or T; NULL: every observation)
+ * says whether an observation counts.  In this order: a masked observation is skipped; one with an invalid code is skipped; one whose
+ * valid code is not in vocab is skipped and *unmatched (int64) += 1.
+ * frl_strata_contingency: rows int32 [B][Tr][P] (Tr 1 or T), 1 <= R <= 4096, R G <= 2^24.  A label outside [0, R) is skipped and
+ * *rejected (int64) += 1; else table [R][G] (int64) += 1 at (label, column of the code).  Integer atomics only (in LDS up to 8192 cells,
+ * 64-bit in memory beyond): the table is exact and order-independent.  table, unmatched and rejected are zeroed by the caller before the
+ * first call; calls accumulate.
+ * frl_strata_moments: X float32 [B][T][P][D], pivot [D], over the groups [g0, g0 + Gc) of the vocabulary (observations of other groups
+ * are skipped, so a long vocabulary is walked in windows; unmatched may be NULL, for all windows but one).  1 <= D <= 128,
+ * 1 <= Gc <= 128, Gc D <= 8192.  With y = x - pivot in float32:
+ *   temporal = 0: per unmasked observation, count [G] (int64) += 1, S1 [G][D] (double) += y, S2 [G][D] += y^2.  SW is not touched.
+ *   temporal = 1: one row per unmasked pixel (the mask is [B][1][P]): mu = (sum_t y_t, float32 in t order) / T and
+ *   w = sum_t (y_t - mu)^2 / T (the population variance, exactly 0 at T = 1); count += 1, S1 += mu, S2 += mu^2, SW [G][D] += w.
+ * The sums are exact float32 fmaf chains inside a workgroup; the workgroups' slabs are added in slab order in double, so every result is
+ * bit-identical from run to run for one value of workgroups (0 = the library's choice, else 1..4096).  X must be finite in every row that
+ * is not skipped.  Tiles of 64 pixels with nothing to add are not read.  count, S1, S2, SW are zeroed by the caller before the first call.
+ * Limits: else -2.  Workspace (16-byte aligned) for frl_strata_moments: frl_strata_workspace_bytes(Gc, D, temporal, workgroups), which is
+ * enough for every window of at most Gc groups (else -4); the table call needs none. */
+size_t frl_strata_workspace_bytes(int Gc, int D, int temporal, int workgroups);
+int frl_strata_contingency(const int32_t* rows, int Tr, const void* codes, int codes_float, const unsigned char* mask, int Tm, const int32_t* vocab,
+                           int G, int B, int T, int64_t P, int R, int workgroups, int64_t* table, int64_t* unmatched, int64_t* rejected,
+                           frl_stream_t stream);
+int frl_strata_moments(const float* X, const void* codes, int codes_float, const unsigned char* mask, int Tm, const int32_t* vocab, int G, int g0,
+                       int Gc, int B, int T, int64_t P, int D, const float* pivot, int temporal, int workgroups, int64_t* count, double* S1,
+                       double* S2, double* SW, int64_t* unmatched, void* ws, size_t ws_bytes, frl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2446,3 +2446,125 @@ def probe_evaluate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor,
     check(_lib.load().frl_probe_evaluate(*_probe_args(a, bs, y, mask, dims), _p(pivot), _p(wc), _p(bc), int(workgroups), _p(e), _p(n), _p(pred),
                                          _p(ws), ws.numel(), _stream()), "frl_probe_evaluate")
     return pred
+
+
+# ----------------------------------------------------------------------------------------------
+# EVT-stratified diagnostics (csrc/strata.hip)
+# ----------------------------------------------------------------------------------------------
+STRATA_MAX_G, STRATA_MAX_R, STRATA_MAX_CELLS = 4095, 4096, 1 << 24
+STRATA_MAX_GC, STRATA_MAX_D, STRATA_MAX_GD, STRATA_MAX_WORKGROUPS = 128, 128, 8192, 4096
+
+
+def chk_strata_table_dims(r: int, g: int, workgroups: int = 0, name: str = "strata_contingency"):
+    """The size limits of frl_strata_contingency that need no data (ValueError)."""
+    if not 1 <= int(g) <= STRATA_MAX_G:
+        raise ValueError(f"{name}: supports 1 <= G <= {STRATA_MAX_G} codes in the vocabulary, got {g}")
+    if not 1 <= int(r) <= STRATA_MAX_R:
+        raise ValueError(f"{name}: supports 1 <= R <= {STRATA_MAX_R} row labels, got {r}")
+    if int(r) * int(g) > STRATA_MAX_CELLS:
+        raise ValueError(f"{name}: supports R * G <= 2^24 cells, got {r} * {g}")
+    if not 0 <= int(workgroups) <= STRATA_MAX_WORKGROUPS:
+        raise ValueError(f"{name}: workgroups must be in 0..{STRATA_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+
+
+def chk_strata_moment_dims(gc: int, d: int, workgroups: int = 0, name: str = "strata_moments"):
+    """The size limits of frl_strata_moments that need no data (ValueError)."""
+    if not 1 <= int(d) <= STRATA_MAX_D:
+        raise ValueError(f"{name}: supports 1 <= D <= {STRATA_MAX_D} columns, got {d}")
+    if not 1 <= int(gc) <= STRATA_MAX_GC:
+        raise ValueError(f"{name}: supports a window of 1 <= Gc <= {STRATA_MAX_GC} groups, got {gc}")
+    if int(gc) * int(d) > STRATA_MAX_GD:
+        raise ValueError(f"{name}: supports Gc * D <= {STRATA_MAX_GD}, got {gc} * {d}")
+    if not 0 <= int(workgroups) <= STRATA_MAX_WORKGROUPS:
+        raise ValueError(f"{name}: workgroups must be in 0..{STRATA_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+
+
+def _chk_strata_keys(name: str, codes: torch.Tensor, mask: Optional[torch.Tensor], vocab: torch.Tensor, b: int, t: int, p: int):
+    if codes.dtype not in (torch.int32, torch.float32) or tuple(codes.shape) != (b, p) or not codes.is_contiguous():
+        raise ValueError(f"{name}: codes must be a contiguous int32 or float32 [B, P] = [{b}, {p}] tensor, got {codes.dtype} {tuple(codes.shape)}")
+    if vocab.dtype != torch.int32 or vocab.dim() != 1 or not vocab.is_contiguous():
+        raise ValueError(f"{name}: vocab must be a contiguous int32 [G] tensor, got {vocab.dtype} {tuple(vocab.shape)}")
+    if not 1 <= vocab.numel() <= STRATA_MAX_G:
+        raise ValueError(f"{name}: supports 1 <= G <= {STRATA_MAX_G} codes in the vocabulary, got {vocab.numel()}")
+    if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 3 or mask.shape[0] != b or mask.shape[2] != p or mask.shape[1] not in (1, t)
+                             or not mask.is_contiguous()):
+        raise ValueError(f"{name}: mask must be a contiguous uint8 [B, Tm, P] = [{b}, 1 or {t}, {p}] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    if b < 1 or t < 1 or p < 1:
+        raise ValueError(f"{name}: empty input, B = {b}, T = {t}, P = {p}")
+    if b * t * p >= 2 ** 31:
+        raise ValueError(f"{name}: supports B * T * P < 2^31 observations, got {b * t * p}")
+
+
+def _chk_strata_device(name: str, first: torch.Tensor, *rest):
+    for s in (first,) + rest:
+        if s is not None and not s.is_cuda:
+            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+        if s is not None and s.device != first.device:
+            raise ValueError(f"{name}: all tensors must be on one device")
+
+
+def strata_workspace(gc: int, d: int, temporal: bool, device, workgroups: int = 0) -> torch.Tensor:
+    """A workspace for frl_strata_moments (the slabs of partial sums between the pass and its reduction)."""
+    chk_strata_moment_dims(gc, d, workgroups, "strata_workspace")
+    if not torch.device(device).type == "cuda":
+        raise _lib.FrlHipError("strata_workspace: the device must be a GPU (no CPU fallback)")
+    return torch.empty(max(_lib.load().frl_strata_workspace_bytes(int(gc), int(d), int(bool(temporal)), int(workgroups)), 256), dtype=torch.uint8,
+                       device=device)
+
+
+@_timed("strata_contingency")
+def strata_contingency(rows: torch.Tensor, codes: torch.Tensor, mask: Optional[torch.Tensor], vocab: torch.Tensor, table: torch.Tensor,
+                       unmatched: torch.Tensor, rejected: torch.Tensor, workgroups: int = 0) -> None:
+    """table int64 [R, G] += the counts of (rows [B, Tr, P] int32, column of codes [B, P]) over the unmasked observations; unmatched and
+    rejected int64 [1] += the skipped ones (include/frl_hip.h: frl_strata_contingency).  No host read."""
+    name = "strata_contingency"
+    if rows.dim() != 3 or rows.dtype != torch.int32 or not rows.is_contiguous():
+        raise ValueError(f"{name}: rows must be a contiguous int32 [B, Tr, P] tensor, got {rows.dtype} {tuple(rows.shape)}")
+    b, tr, p = rows.shape
+    t = max(tr, 1 if mask is None or mask.dim() != 3 else mask.shape[1])
+    if tr not in (1, t):
+        raise ValueError(f"{name}: rows {tuple(rows.shape)} and mask {tuple(mask.shape)} differ in T")
+    _chk_strata_keys(name, codes, mask, vocab, b, t, p)
+    if table.dim() != 2 or table.shape[1] != vocab.numel():
+        raise ValueError(f"{name}: table must be [R, G] = [R, {vocab.numel()}], got {tuple(table.shape)}")
+    r, g = table.shape
+    chk_strata_table_dims(r, g, workgroups, name)
+    _chk_strata_device(name, rows, codes, mask, vocab, table, unmatched, rejected)
+    _chk_probe_vec(name, "table", table, (r, g), torch.int64, rows.device)
+    _chk_probe_vec(name, "unmatched", unmatched, (1,), torch.int64, rows.device)
+    _chk_probe_vec(name, "rejected", rejected, (1,), torch.int64, rows.device)
+    check(_lib.load().frl_strata_contingency(_p(rows), tr, _p(codes), int(codes.dtype == torch.float32), _p(mask), 1 if mask is None else mask.shape[1],
+                                             _p(vocab), g, b, t, p, r, int(workgroups), _p(table), _p(unmatched), _p(rejected), _stream()),
+          "frl_strata_contingency")
+
+
+@_timed("strata_moments")
+def strata_moments(x: torch.Tensor, codes: torch.Tensor, mask: Optional[torch.Tensor], vocab: torch.Tensor, g0: int, gc: int, pivot: torch.Tensor,
+                   count: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, sw: Optional[torch.Tensor], unmatched: Optional[torch.Tensor],
+                   ws: torch.Tensor, temporal: bool = False, workgroups: int = 0) -> None:
+    """count int64 [G], S1, S2 (and SW, temporal) float64 [G, D] += the moments of x [B, T, P, D] - pivot over the groups [g0, g0 + gc) of
+    the vocabulary (include/frl_hip.h: frl_strata_moments).  No host read."""
+    name = "strata_moments"
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be a contiguous float32 [B, T, P, D] tensor, got {x.dtype} {tuple(x.shape)}")
+    b, t, p, d = x.shape
+    chk_strata_moment_dims(gc, d, workgroups, name)
+    _chk_strata_keys(name, codes, mask, vocab, b, t, p)
+    g = vocab.numel()
+    if not 0 <= int(g0) <= g - int(gc):
+        raise ValueError(f"{name}: the window [{g0}, {g0} + {gc}) must lie in the vocabulary of {g} codes")
+    if temporal and mask is not None and mask.shape[1] != 1:
+        raise ValueError(f"{name}: the temporal mode takes a per-pixel mask [B, 1, P], got {tuple(mask.shape)}")
+    if temporal and sw is None:
+        raise ValueError(f"{name}: the temporal mode needs SW")
+    _chk_strata_device(name, x, codes, mask, vocab, pivot, count, s1, s2, sw, unmatched, ws)
+    _chk_probe_vec(name, "pivot", pivot, (d,), torch.float32, x.device)
+    _chk_probe_vec(name, "count", count, (g,), torch.int64, x.device)
+    for what, s in (("S1", s1), ("S2", s2), ("SW", sw)):
+        if s is not None:
+            _chk_probe_vec(name, what, s, (g, d), torch.float64, x.device)
+    if unmatched is not None:
+        _chk_probe_vec(name, "unmatched", unmatched, (1,), torch.int64, x.device)
+    check(_lib.load().frl_strata_moments(_p(x), _p(codes), int(codes.dtype == torch.float32), _p(mask), 1 if mask is None else mask.shape[1], _p(vocab),
+                                         g, int(g0), int(gc), b, t, p, d, _p(pivot), int(bool(temporal)), int(workgroups), _p(count), _p(s1), _p(s2),
+                                         _p(sw), _p(unmatched), _p(ws), ws.numel(), _stream()), "frl_strata_moments")
