@@ -111,7 +111,7 @@ def _check_params(got, want, b, scale=1.0, what=""):
 @pytest.mark.parametrize("case", G.STEP_CASES)
 def test_one_em_step(case):
     r = _ref(case)
-    for wg in (1, 2, 0):
+    for wg in (1, 2, 3, 0):                                                      # 3 slabs: no multiple of the four parts of the slab sum
         got = _gpu_step(r["inp"], wg)
         again = _gpu_step(r["inp"], wg)
         assert all(np.array_equal(a, b) for a, b in zip(got[:3], again[:3])) and got[3] == again[3], f"workgroups={wg}: two runs differ"

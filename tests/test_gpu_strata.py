@@ -233,7 +233,7 @@ def test_moments_pivot_matters(temporal):
 
 
 @pytest.mark.parametrize("temporal", [False, True], ids=["observations", "temporal"])
-@pytest.mark.parametrize("shape,g", [((2, 5, 300, 12), 20), ((1, 3, 70, 128), 127)])
+@pytest.mark.parametrize("shape,g", [((2, 5, 300, 12), 20), ((1, 3, 70, 128), 127), ((1, 2, 70, 6), 20)])   # D = 6: the scalar staging path
 def test_moments_for_any_grid_and_bit_identical(shape, g, temporal):
     c = SC.moment_case(shape, g, seed=3)
     pivot = np.full(shape[3], 0.25, np.float32)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
 
 int frl_fail(int code, const char* msg);           // records thread-local message, returns code
 int frl_check_launch(const char* what);            // hipGetLastError() -> 0 or negative code
@@ -53,6 +54,19 @@ static inline unsigned frl_grid(int64_t work, int per_block, int cap) {
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (unsigned)g;
+}
+
+static inline int frl_failf(int code, const char* fmt, const char* a, const char* b = "") {   // frl_fail(code, fmt % (a, b))
+  char msg[200];
+  snprintf(msg, sizeof(msg), fmt, a, b);
+  return frl_fail(code, msg);
+}
+// gmm.hip, probe.hip, strata.hip: `workgroups` (0: the library's choice) slabs in a workspace of the caller's: the limit and the two refusals
+#define FRL_MAX_WG 4096
+static inline bool frl_wg_in_range(int wg) { return wg >= 0 && wg <= FRL_MAX_WG; }
+static inline int frl_check_workgroups(const char* what, int wg) { return frl_wg_in_range(wg) ? 0 : frl_failf(-2, "%s: workgroups must be in 0..4096 (0: the library's choice)", what); }
+static inline int frl_check_workspace(const char* what, const void* ws, size_t ws_bytes, size_t need) {
+  return ws && !((uintptr_t)ws & 15) && ws_bytes >= need ? 0 : frl_failf(-4, "%s: workspace too small or not 16-byte aligned", what);
 }
 
 // moment kernels that give each workgroup a contiguous range of rows, staged rows_per_tile at a time (vicreg.hip, leakage.hip): the

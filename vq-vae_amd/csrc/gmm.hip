@@ -8,22 +8,20 @@
 // Both run on v_mfma_f32_16x16x4_f32 (exact float32, an fmaf chain in k order).  A workgroup of four waves walks 64-row tiles in a
 // grid-stride loop: a tile is staged once in LDS (pivot subtracted), each wave forms lp, the softmax and w r for its 16 rows and
 // parks w r in LDS transposed; then the waves share out the (K/16) x (2D/16) moment blocks, whose accumulators stay in registers
-// for the whole loop.  Responsibilities never reach memory.  Each workgroup writes one slab of partial sums; frl_gmm_m_step adds the
-// slabs in slab order in double and forms the parameters, the lower bound and the convergence flag on the device, so the host can
-// enqueue iterations blind.  No float atomics anywhere: every result is bit-identical from run to run.
+// for the whole loop (the moment half is the scheme of frl_moments.hpp).  Responsibilities never reach memory.  Each workgroup writes one
+// slab of partial sums; frl_gmm_m_step adds the slabs in the order of moment_slab_sum and forms the parameters, the lower bound and the
+// convergence flag on the device, so the host can enqueue iterations blind.  No float atomics anywhere: results are bit-identical run to run.
 //
 // The state the iteration carries is (pi, m = mu - p, var): mu itself is only an output, so data far from the origin loses nothing
 // to the rounding of mu.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
-#include <cstdio>
+#include "frl_moments.hpp"
 
 #define GMM_MAX_K 128
 #define GMM_MAX_D 128
 #define GMM_MAX_KD 8192
-#define GMM_ROWS 64        // rows of a tile: 16 per wave
 #define GMM_RS 68          // row stride of the transposed w r tile [Kp][64]: lanes (k, row) hit 64 distinct banks
-#define GMM_MAX_WG 4096
 #define GMM_LDS_MAX (160 * 1024)
 #define GMM_PIVOT_WG 256
 // 1: the variants with at most 8 moment blocks per wave are compiled for two waves per SIMD (two workgroups per CU), which costs a few
@@ -43,8 +41,6 @@ struct GmmDims {
   size_t lds;
 };
 
-// row stride of the y tile: the smallest ys >= Dp with ys mod 64 in {20, 44}: the lp read (16 rows x 4 columns per wave) is then
-// conflict-free and the moment read (4 rows x 16 columns) nearly so
 GmmDims gmm_dims(int D, int K) {
   GmmDims g;
   g.KB = (K + 15) / 16;
@@ -52,18 +48,16 @@ GmmDims gmm_dims(int D, int K) {
   g.Kp = 16 * g.KB;
   g.Dp = 16 * g.DB;
   g.NS = 4 * g.DB;
-  int ys = g.Dp;
-  while (ys % 64 != 20 && ys % 64 != 44) ys += 4;
-  g.ys = ys;
+  const int ys = g.ys = frl_tile_stride(g.Dp);
   g.nblk = g.KB * 2 * g.DB;
   g.slabF = g.nblk * 256 + g.Kp;
-  g.lds = sizeof(float) * ((size_t)2 * g.Kp * g.Dp + g.Kp + g.Dp + (size_t)GMM_ROWS * ys + (size_t)g.Kp * GMM_RS + GMM_ROWS);
+  g.lds = sizeof(float) * ((size_t)2 * g.Kp * g.Dp + g.Kp + g.Dp + (size_t)MOMENT_ROWS * ys + (size_t)g.Kp * GMM_RS + MOMENT_ROWS);
   return g;
 }
 
 int gmm_grid(int64_t N, const GmmDims& g, int workgroups) {
   if (workgroups > 0) return workgroups;
-  const int64_t ntiles = (N + GMM_ROWS - 1) / GMM_ROWS;
+  const int64_t ntiles = (N + MOMENT_ROWS - 1) / MOMENT_ROWS;
   const int64_t cap = g.lds <= 80 * 1024 ? 512 : 256;                            // two workgroups per CU where LDS allows
   return (int)(ntiles < cap ? ntiles : cap);
 }
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
   float* ak = PB + Kp * Dp;                                                      // [Kp], -inf beyond K
   float* piv = ak + Kp;                                                          // [Dp]
   float* yt = piv + Dp;                                                          // [64][ys]
-  float* rT = yt + GMM_ROWS * ys;                                                // [Kp][GMM_RS]
+  float* rT = yt + MOMENT_ROWS * ys;                                             // [Kp][GMM_RS]
   float* wrow = rT + Kp * GMM_RS;                                                // [64]
 
   for (int i = tid; i < Kp * Dp; i += 256) {
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
     ak[k] = a;
   }
   for (int d = tid; d < Dp; d += 256) piv[d] = d < D ? pivot[d] : 0.f;
-  for (int i = tid; i < GMM_ROWS * ys; i += 256) yt[i] = 0.f;                   // the padding columns stay zero
+  for (int i = tid; i < MOMENT_ROWS * ys; i += 256) yt[i] = 0.f;                // the padding columns stay zero
 
   f32x4 macc[NBM];
   float s0[KBM][4];
@@ -170,12 +164,12 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
     for (int r = 0; r < 4; ++r) s0[kb][r] = 0.f;
   double dl = 0.0, dw = 0.0;
 
-  const int ntiles = (N + GMM_ROWS - 1) / GMM_ROWS, tileF = GMM_ROWS * D;
+  const int ntiles = (N + MOMENT_ROWS - 1) / MOMENT_ROWS, tileF = MOMENT_ROWS * D;
   f32x4 pre[8];
   float wpre = 0.f;
   auto fetch = [&](int tile) {
-    const int row0 = tile * GMM_ROWS;
-    const int valid = (N - row0 < GMM_ROWS ? N - row0 : GMM_ROWS) * D;          // floats of the tile that exist
+    const int row0 = tile * MOMENT_ROWS;
+    const int valid = (N - row0 < MOMENT_ROWS ? N - row0 : MOMENT_ROWS) * D;    // floats of the tile that exist
     const float* base = X + (size_t)row0 * D;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -189,11 +183,11 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
           if (e0 + j < valid) pre[c][j] = base[e0 + j];
       }
     }
-    if (tid < GMM_ROWS) wpre = row0 + tid < N ? (w ? w[row0 + tid] : 1.f) : 0.f;
+    if (tid < MOMENT_ROWS) wpre = row0 + tid < N ? (w ? w[row0 + tid] : 1.f) : 0.f;
   };
   auto commit = [&](int tile) {
-    const int row0 = tile * GMM_ROWS;
-    const int valid = (N - row0 < GMM_ROWS ? N - row0 : GMM_ROWS) * D;
+    const int row0 = tile * MOMENT_ROWS;
+    const int valid = (N - row0 < MOMENT_ROWS ? N - row0 : MOMENT_ROWS) * D;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const int e0 = (c * 256 + tid) * 4;
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
         }
       }
     }
-    if (tid < GMM_ROWS) wrow[tid] = wpre;
+    if (tid < MOMENT_ROWS) wrow[tid] = wpre;
   };
 
   if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
@@ -282,7 +276,7 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
       inv = 1.f / sum;
     }
     if (MODE == GMM_SCORE) {
-      const int64_t row = (int64_t)tile * GMM_ROWS + rl;
+      const int64_t row = (int64_t)tile * MOMENT_ROWS + rl;
       if (row < N) {
         if (lg == 0) {
           lse_out[row] = lse;
@@ -330,7 +324,7 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
         const float* ap = rT + (kb * 16 + lr) * GMM_RS + lg;
         const float* vp = yt + lg * ys + (sq ? cb - DB : cb) * 16 + lr;
 #pragma unroll 4
-        for (int st = 0; st < GMM_ROWS / 4; ++st) {
+        for (int st = 0; st < MOMENT_ROWS / 4; ++st) {
           float v = vp[4 * st * ys];
           if (sq) v *= v;
           macc[i] = mfma16(ap[4 * st], v, macc[i]);
@@ -344,7 +338,7 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
   const int nblk = KB * 2 * DB, slabF = nblk * 256 + Kp;
   float* slab = slabs + (size_t)blockIdx.x * slabF;
 #pragma unroll
-  for (int i = 0; i < NBM; ++i) {
+  for (int i = 0; i < NBM; ++i) {                                                // (written out: DESIGN 6v)
     const int b = wave + 4 * i;
     if (b < nblk) *reinterpret_cast<f32x4*>(slab + ((size_t)b * 64 + lane) * 4) = macc[i];
   }
@@ -375,22 +369,14 @@ __global__ __launch_bounds__(256, (GMM_FORCE_OCC && NBM <= 8 ? 2 : 1)) void gmm_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// M step: the slabs added in slab order in double (64 elements x 4 interleaved parts per workgroup), then one workgroup forms the
-// parameters, the lower bound and the flag
+// M step: the slabs added in double (moment_slab_sum), then one workgroup forms the parameters, the lower bound and the flag
 // ---------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gmm_m_reduce_kernel(const float* __restrict__ slabs, int G, int slabF, const int* __restrict__ state,
                                                            double* __restrict__ red) {
   if (state[1]) return;
-  __shared__ double part[4][64];
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), p = threadIdx.x >> 6;
-  double s = 0.0;
-  if (e < slabF) {
-#pragma unroll 4
-    for (int g = p; g < G; g += 4) s += (double)slabs[(size_t)g * slabF + e];
-  }
-  part[p][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (p == 0 && e < slabF) red[e] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+  const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+  const double sum = moment_slab_sum(slabs, G, slabF, e, e < slabF);             // the S0 tail of a slab need not fill 64 elements
+  if (threadIdx.x < 64 && e < slabF) red[e] = sum;
 }
 
 __global__ __launch_bounds__(256) void gmm_m_final_kernel(const double* __restrict__ red, const double* __restrict__ dsl, int G, int D, int K,
@@ -420,8 +406,7 @@ __global__ __launch_bounds__(256) void gmm_m_final_kernel(const double* __restri
   __syncthreads();
   for (int e = tid; e < K * D; e += 256) {
     const int k = e / D, d = e - k * D;
-    const int kb = k >> 4, lg = (k & 15) >> 2, r = k & 3, cb = d >> 4, lr = d & 15;
-    const size_t i1 = ((size_t)(kb * nb2 + cb) * 64 + lg * 16 + lr) * 4 + r, i2 = i1 + (size_t)DB * 256;
+    const size_t i1 = moment_frag_index((k >> 4) * nb2 + (d >> 4), k & 15, d & 15), i2 = i1 + (size_t)DB * 256;   // y | y^2 are DB blocks apart
     const double n = nk[k];
     if (mode == GMM_M_LLOYD) {
       if (n > 0.0) {                                                             // a centre without a row keeps its value
@@ -500,16 +485,13 @@ __global__ __launch_bounds__(256) void phase_summary_kernel(const float* __restr
 namespace {
 
 int gmm_check(const char* what, int64_t N, int D, int K) {
-  static thread_local char msg[160];
   const char* why = nullptr;
   if (K < 1 || K > GMM_MAX_K) why = "1 <= K <= 128 components";
   else if (D < 1 || D > GMM_MAX_D) why = "1 <= D <= 128 columns";
   else if ((int64_t)K * D > GMM_MAX_KD) why = "K * D <= 8192";
   else if (N < K) why = "N >= K rows";
   else if (N > 0x7fffffffll) why = "N < 2^31 rows";
-  if (!why) return 0;
-  snprintf(msg, sizeof(msg), "%s: needs %s", what, why);
-  return frl_fail(-2, msg);
+  return why ? frl_failf(-2, "%s: needs %s", what, why) : 0;
 }
 
 typedef void (*gmm_e_fn)(const float*, const float*, int, int, int, int, int, int, int, const float*, const float*, const float*, const float*,
@@ -542,7 +524,7 @@ extern "C" {
 
 // See include/frl_hip.h.
 size_t frl_gmm_workspace_bytes(int64_t N, int D, int K, int workgroups) {
-  if (N < 1 || D < 1 || D > GMM_MAX_D || K < 1 || K > GMM_MAX_K || workgroups < 0 || workgroups > GMM_MAX_WG) return 0;
+  if (N < 1 || D < 1 || D > GMM_MAX_D || K < 1 || K > GMM_MAX_K || !frl_wg_in_range(workgroups)) return 0;
   const GmmDims g = gmm_dims(D, K);
   const size_t em = gmm_ws(nullptr, gmm_grid(N, g, workgroups), g).bytes;
   const size_t pv = sizeof(double) * GMM_PIVOT_WG * (size_t)D;
@@ -563,12 +545,12 @@ int frl_gmm_pivot(const float* X, int64_t N, int D, float* pivot, void* ws, size
 int frl_gmm_em_step(const float* X, const float* w, int64_t N, int D, int K, const float* pivot, const float* weights, const float* means_c,
                     const float* vars, int hard, int workgroups, const int* state, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (int rc = gmm_check("gmm_em_step", N, D, K)) return rc;
-  if (workgroups < 0 || workgroups > GMM_MAX_WG) return frl_fail(-2, "gmm_em_step: workgroups must be in 0..4096 (0: the library's choice)");
+  if (int rc = frl_check_workgroups("gmm_em_step", workgroups)) return rc;
   if (!X || !pivot || !weights || !means_c || !vars || !state) return frl_fail(-2, "gmm_em_step: null pointer");
   const GmmDims g = gmm_dims(D, K);
   const int G = gmm_grid(N, g, workgroups);
   const GmmWs o = gmm_ws(ws, G, g);
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < o.bytes) return frl_fail(-4, "gmm_em_step: workspace too small or not 16-byte aligned");
+  if (int rc = frl_check_workspace("gmm_em_step", ws, ws_bytes, o.bytes)) return rc;
   if (int rc = gmm_launch_e(hard ? GMM_HARD : GMM_SOFT, X, w, N, D, K, pivot, weights, means_c, vars, state, G, o.slabs, o.dsl, nullptr, nullptr,
                             nullptr, stream))
     return rc;
@@ -579,14 +561,14 @@ int frl_gmm_m_step(int64_t N, int D, int K, const float* pivot, float* weights, 
                    double tol, int mode, double* history, int max_iter, int* state, int workgroups, void* ws, size_t ws_bytes,
                    hipStream_t stream) {
   if (int rc = gmm_check("gmm_m_step", N, D, K)) return rc;
-  if (workgroups < 0 || workgroups > GMM_MAX_WG) return frl_fail(-2, "gmm_m_step: workgroups must be in 0..4096 (0: the library's choice)");
+  if (int rc = frl_check_workgroups("gmm_m_step", workgroups)) return rc;
   if (mode < GMM_M_EM || mode > GMM_M_INIT) return frl_fail(-2, "gmm_m_step: mode must be 0 (EM), 1 (Lloyd) or 2 (initial parameters)");
   if (!pivot || !weights || !means || !means_c || !vars || !state) return frl_fail(-2, "gmm_m_step: null pointer");
   if (mode == GMM_M_EM && (!history || max_iter < 1)) return frl_fail(-2, "gmm_m_step: the EM mode needs history [max_iter], max_iter >= 1");
   const GmmDims g = gmm_dims(D, K);
   const int G = gmm_grid(N, g, workgroups);
   const GmmWs o = gmm_ws(ws, G, g);
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < o.bytes) return frl_fail(-4, "gmm_m_step: workspace too small or not 16-byte aligned");
+  if (int rc = frl_check_workspace("gmm_m_step", ws, ws_bytes, o.bytes)) return rc;
   FRL_LAUNCH(gmm_m_reduce_kernel, dim3((unsigned)((g.slabF + 63) / 64)), dim3(256), 0, stream, (const float*)o.slabs, G, g.slabF,
              (const int*)state, o.red);
   FRL_LAUNCH(gmm_m_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)o.red, (const double*)o.dsl, G, D, K, g.KB, g.DB, pivot, weights,
@@ -599,8 +581,8 @@ int frl_gmm_score(const float* X, int64_t N, int D, int K, const float* pivot, c
   if (K < 1 || K > GMM_MAX_K || D < 1 || D > GMM_MAX_D || (int64_t)K * D > GMM_MAX_KD) return gmm_check("gmm_score", GMM_MAX_K, D, K);
   if (N < 1 || N > 0x7fffffffll) return frl_fail(-2, "gmm_score: needs 1 <= N < 2^31 rows");
   if (!X || !pivot || !weights || !means_c || !vars || !lse || !labels) return frl_fail(-2, "gmm_score: null pointer");
-  const int64_t ntiles = (N + GMM_ROWS - 1) / GMM_ROWS;
-  const int G = (int)(ntiles < GMM_MAX_WG ? ntiles : GMM_MAX_WG);
+  const int64_t ntiles = (N + MOMENT_ROWS - 1) / MOMENT_ROWS;
+  const int G = (int)(ntiles < FRL_MAX_WG ? ntiles : FRL_MAX_WG);
   if (int rc = gmm_launch_e(GMM_SCORE, X, nullptr, N, D, K, pivot, weights, means_c, vars, nullptr, G, nullptr, nullptr, lse, labels, resp, stream))
     return rc;
   return frl_check_launch("gmm_score");

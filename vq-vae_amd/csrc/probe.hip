@@ -5,24 +5,20 @@
 // A [B][Ta][P][Da], Bs [B][Tb][P][Db] (T_s = 1: the row is shared by all t), its targets from Y [B][Ty][P][Cy], and mask [B][P] (uint8,
 // shared over t) says whether it counts.  With v = [x - p_x | y - p_y | m] (p: a fixed pivot near the column means, subtracted in
 // float32; the whole row is zero where m = 0) one product v^T v holds everything a ridge fit needs: the scatter, the column sums and,
-// in its last entry, the count.  frl_probe_accumulate forms it as gmm_e_kernel forms its moments: a workgroup of four waves walks
-// tiles of 64 consecutive pixels of one (b, t) in a grid-stride loop, stages a tile once in LDS, and the waves share out the 16 x 16
-// blocks of the upper triangle on v_mfma_f32_16x16x4_f32 (exact float32, an fmaf chain in row order) with accumulators in registers
-// for the whole loop.  A tile whose 64 mask bytes are zero is skipped before anything of it is read.  Each workgroup writes one slab;
-// a second kernel adds the slabs in a fixed order in double into the running state and mirrors it.  The count is a sum of popcounts
-// in int64.  No float atomics: two runs on the same inputs give the same bits.
+// in its last entry, the count.  frl_probe_accumulate forms it by the staged-tile scheme of frl_moments.hpp over tiles of 64 consecutive
+// pixels of one (b, t), the product being the 16 x 16 blocks of the upper triangle (exact float32, an fmaf chain in row order).  A tile
+// whose 64 mask bytes are zero is skipped before anything of it is read.  The slabs are added in the order of moment_slab_sum into the
+// running state, which is then mirrored.  The count is a sum of popcounts in int64.  No float atomics: two runs give the same bits.
 // frl_probe_pivot forms the masked column means the same way (tiles staged in LDS, column sums in double, workgroups added in a
 // fixed order).  frl_probe_evaluate stages the tile with the next one's loads already in registers, gives lane = pixel and
 // wave = targets w, w + 4, .., and runs pred = bc + (x - p) Wc as a float32 fmaf chain in d order with SSE, sum (y - q) and
 // sum (y - q)^2 in double per lane.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
-#include <cstdio>
+#include "frl_moments.hpp"
 
 #define PROBE_MAX_D 128
 #define PROBE_MAX_CY 16
-#define PROBE_ROWS 64
-#define PROBE_MAX_WG 4096
 #define PROBE_PIVOT_WG 1024
 #define PROBE_EVAL_WG 1024
 
@@ -42,20 +38,16 @@ struct ProbeDims {
   size_t lds;
 };
 
-// row stride of the staged tile: the rule of gmm_dims (gmm.hip): the smallest ys >= 16 CB with ys mod 64 in {20, 44}, so that the
-// 4-row x 16-column operand read of the MFMA loop is nearly conflict-free
 ProbeDims probe_dims(int D, int Cy) {
   ProbeDims g;
   g.D = D;
   g.C = D + Cy;
   g.C1 = g.C + 1;
   g.CB = (g.C1 + 15) / 16;
-  int ys = 16 * g.CB;
-  while (ys % 64 != 20 && ys % 64 != 44) ys += 4;
-  g.ys = ys;
+  const int ys = g.ys = frl_tile_stride(16 * g.CB);
   g.nblk = g.CB * (g.CB + 1) / 2;
   g.slabF = g.nblk * 256;
-  g.lds = sizeof(float) * ((size_t)PROBE_ROWS * ys + 16 * g.CB);
+  g.lds = sizeof(float) * ((size_t)MOMENT_ROWS * ys + 16 * g.CB);
   return g;
 }
 
@@ -79,17 +71,9 @@ __device__ __forceinline__ void probe_block(int b, int CB, int& ib, int& jb) {
   jb = ib + b;
 }
 
-__device__ __forceinline__ void probe_tile(const ProbeIn& q, int tile, int& b, int& t, int& p0) {
-  const int bt = tile / q.PT;
-  p0 = (tile - bt * q.PT) * PROBE_ROWS;
-  b = bt / q.T;
-  t = bt - b * q.T;
-}
-
 // the mask bits of a tile, one per pixel, the same in every wave
 __device__ __forceinline__ unsigned long long probe_mask_bits(const ProbeIn& q, int b, int p0, int lane) {
-  const int valid = q.P - p0 < PROBE_ROWS ? q.P - p0 : PROBE_ROWS;
-  const unsigned char m = lane < valid ? q.mask[(size_t)b * q.P + p0 + lane] : (unsigned char)0;
+  const unsigned char m = lane < moment_tile_rows(q.P, p0) ? q.mask[(size_t)b * q.P + p0 + lane] : (unsigned char)0;
   return __ballot(m != 0);
 }
 
@@ -99,7 +83,7 @@ __device__ __forceinline__ void probe_stage(float* vt, int ys, const float* piv,
                                             bool centre, const ProbeIn& q, int b, int t, int p0, unsigned long long rows, int tid) {
   const float* base = src + ((size_t)((int64_t)b * Ts + (Ts > 1 ? t : 0)) * q.P + p0) * Dn;
   if (vec) {
-    const int q4 = Dn >> 2, n4 = PROBE_ROWS * q4;
+    const int q4 = Dn >> 2, n4 = MOMENT_ROWS * q4;
     for (int e = tid; e < n4; e += 256) {
       const int row = e / q4, c = (e - row * q4) * 4;
       f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -114,7 +98,7 @@ __device__ __forceinline__ void probe_stage(float* vt, int ys, const float* piv,
     }
     return;
   }
-  const int n = PROBE_ROWS * Dn;
+  const int n = MOMENT_ROWS * Dn;
   for (int e = tid; e < n; e += 256) {
     const int row = e / Dn, c = e - row * Dn;
     float v = 0.f;
@@ -157,7 +141,7 @@ __device__ __forceinline__ void probe_map(const ProbeIn& q, int ys, int tid, Pro
     const int qq = isA ? qa : qb, e = tid + 256 * (isA ? c : c - M.nA);
     M.row[c] = -1;
     M.goff[c] = M.loff[c] = 0;
-    if (q.fast && e < PROBE_ROWS * qq) {
+    if (q.fast && e < MOMENT_ROWS * qq) {
       const int row = e / qq, c4 = e - row * qq;
       M.row[c] = row;
       M.goff[c] = row * 4 * qq + 4 * c4;
@@ -169,7 +153,7 @@ __device__ __forceinline__ void probe_map(const ProbeIn& q, int ys, int tid, Pro
     const int e = tid + 256 * j;
     M.yrow[j] = -1;
     M.yloff[j] = 0;
-    if (q.fast && e < PROBE_ROWS * q.Cy) {
+    if (q.fast && e < MOMENT_ROWS * q.Cy) {
       const int row = e / q.Cy;
       M.yrow[j] = row;
       M.yloff[j] = row * ys + q.Da + q.Db + (e - row * q.Cy);
@@ -178,10 +162,10 @@ __device__ __forceinline__ void probe_map(const ProbeIn& q, int ys, int tid, Pro
 }
 
 __device__ __forceinline__ void probe_fetch(const ProbeIn& q, const ProbeMap& M, int tile, int tid, int lane, bool all, ProbeRegs& R) {
-  probe_tile(q, tile, R.b, R.t, R.p0);
+  moment_tile(tile, q.PT, q.T, R.b, R.t, R.p0);
   R.rows = probe_mask_bits(q, R.b, R.p0, lane);
-  const int valid = q.P - R.p0 < PROBE_ROWS ? q.P - R.p0 : PROBE_ROWS;
-  R.live = all ? (valid == PROBE_ROWS ? ~0ull : (1ull << valid) - 1ull) : R.rows;
+  const int valid = moment_tile_rows(q.P, R.p0);
+  R.live = all ? (valid == MOMENT_ROWS ? ~0ull : (1ull << valid) - 1ull) : R.rows;
   if (R.live == 0ull || !q.fast) return;
   const float* baseA = q.A + ((size_t)((int64_t)R.b * q.Ta + (q.Ta > 1 ? R.t : 0)) * q.P + R.p0) * q.Da;
   const float* baseB = q.Db ? q.Bs + ((size_t)((int64_t)R.b * q.Tb + (q.Tb > 1 ? R.t : 0)) * q.P + R.p0) * q.Db : baseA;
@@ -306,9 +290,9 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 3 : 2)) void probe_
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lg = lane >> 4;
   const int D = q.Da + q.Db, C = D + q.Cy, nblk = CB * (CB + 1) / 2;
   float* vt = reinterpret_cast<float*>(smem);                                    // [64][ys]
-  float* piv = vt + PROBE_ROWS * ys;                                             // [16 CB]
+  float* piv = vt + MOMENT_ROWS * ys;                                            // [16 CB]
   for (int d = tid; d < 16 * CB; d += 256) piv[d] = d < C ? q.pivot[d] : 0.f;
-  for (int i = tid; i < PROBE_ROWS * ys; i += 256) vt[i] = 0.f;                  // the padding columns stay zero
+  for (int i = tid; i < MOMENT_ROWS * ys; i += 256) vt[i] = 0.f;                 // the padding columns stay zero
 
   f32x4 acc[NBM];
   int oa[NBM], ob[NBM];
@@ -324,7 +308,7 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 3 : 2)) void probe_
 
   for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
     int b, t, p0;
-    probe_tile(q, tile, b, t, p0);
+    moment_tile(tile, q.PT, q.T, b, t, p0);
     const unsigned long long rows = probe_mask_bits(q, b, p0, lane);
     if (rows == 0ull) continue;                                                  // uniform: every wave sees the same 64 mask bytes
     cnt += __popcll(rows);
@@ -332,7 +316,7 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 3 : 2)) void probe_
     probe_stage(vt, ys, piv, q.A, q.Ta, q.Da, 0, q.fast, true, q, b, t, p0, rows, tid);
     if (q.Db) probe_stage(vt, ys, piv, q.Bs, q.Tb, q.Db, q.Da, q.fast, true, q, b, t, p0, rows, tid);
     probe_stage(vt, ys, piv, q.Y, q.Ty, q.Cy, D, false, true, q, b, t, p0, rows, tid);
-    if (tid < PROBE_ROWS) vt[tid * ys + C] = (rows >> tid) & 1ull ? 1.f : 0.f;
+    if (tid < MOMENT_ROWS) vt[tid * ys + C] = (rows >> tid) & 1ull ? 1.f : 0.f;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NBM; ++i) {
@@ -340,43 +324,32 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 3 : 2)) void probe_
         const float* ap = vt + oa[i];
         const float* bp = vt + ob[i];
 #pragma unroll 4
-        for (int st = 0; st < PROBE_ROWS / 4; ++st) acc[i] = mfma16(ap[4 * st * ys], bp[4 * st * ys], acc[i]);
+        for (int st = 0; st < MOMENT_ROWS / 4; ++st) acc[i] = mfma16(ap[4 * st * ys], bp[4 * st * ys], acc[i]);
       }
     }
   }
-  float* slab = slabs + (size_t)blockIdx.x * nblk * 256;
-#pragma unroll
-  for (int i = 0; i < NBM; ++i) {
-    const int blk = wave + 4 * i;
-    if (blk < nblk) *reinterpret_cast<f32x4*>(slab + ((size_t)blk * 64 + lane) * 4) = acc[i];
-  }
+  moment_store_slab<NBM>(slabs + (size_t)blockIdx.x * nblk * 256, acc, wave, lane, nblk);
   if (tid == 0) cnts[blockIdx.x] = cnt;
 }
 
-// the slabs added in double, 64 elements x 4 interleaved parts per workgroup, into S [C1][C1] (both triangles); workgroup 0 adds the count
+// the slabs added in double (moment_slab_sum), 64 elements per workgroup, into S [C1][C1] (both triangles); workgroup 0 adds the count
 __global__ __launch_bounds__(256) void probe_acc_reduce_kernel(const float* __restrict__ slabs, const long long* __restrict__ cnts, int G, int CB,
                                                                int C1, double* __restrict__ S, long long* __restrict__ n) {
-  __shared__ double part[4][64];
   __shared__ long long pc[256];
-  const int slabF = CB * (CB + 1) / 2 * 256;
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), p = threadIdx.x >> 6;
-  double s = 0.0;
-#pragma unroll 4
-  for (int g = p; g < G; g += 4) s += (double)slabs[(size_t)g * slabF + e];
-  part[p][threadIdx.x & 63] = s;
+  const int slabF = CB * (CB + 1) / 2 * 256, e = blockIdx.x * 64 + (threadIdx.x & 63);
   if (blockIdx.x == 0) {
     long long c = 0;
     for (int g = threadIdx.x; g < G; g += 256) c += cnts[g];
     pc[threadIdx.x] = c;
   }
-  __syncthreads();
-  if (p == 0) {
-    const int blk = e >> 8, l = (e >> 2) & 63, r = e & 3;
-    int ib, jb;
+  const double sum = moment_slab_sum(slabs, G, slabF, e, true);                  // its barrier covers pc too
+  if (threadIdx.x < 64) {
+    int blk, row, col, ib, jb;
+    moment_frag_decode(e, blk, row, col);
     probe_block(blk, CB, ib, jb);
-    const int i = ib * 16 + 4 * (l >> 4) + r, j = jb * 16 + (l & 15);
+    const int i = ib * 16 + row, j = jb * 16 + col;
     if (i <= j && j < C1) {
-      const double v = S[(size_t)i * C1 + j] + (((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x]);
+      const double v = S[(size_t)i * C1 + j] + sum;
       S[(size_t)i * C1 + j] = v;
       S[(size_t)j * C1 + i] = v;
     }
@@ -399,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void probe_eval_kernel(ProbeIn q, int ys, c
   const int D = q.Da + q.Db, Cy = q.Cy, C = D + Cy;
   float* Wl = reinterpret_cast<float*>(smem);                                    // [D][4 waves][4]: Wc[d][wave + 4 k], one broadcast read per d
   float* vt = Wl + 16 * D;                                                       // [64][ys]: x - p | y, ys odd
-  float* piv = vt + PROBE_ROWS * ys;                                             // [C]
+  float* piv = vt + MOMENT_ROWS * ys;                                            // [C]
   for (int i = tid; i < 16 * D; i += 256) {
     const int d = i >> 4, c = ((i >> 2) & 3) + 4 * (i & 3);
     Wl[i] = c < Cy ? Wc[d * Cy + c] : 0.f;
@@ -425,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void probe_eval_kernel(ProbeIn q, int ys, c
     }
     const unsigned long long rows = R.rows;
     const int b = R.b, t = R.t, p0 = R.p0;
-    const int valid = q.P - p0 < PROBE_ROWS ? q.P - p0 : PROBE_ROWS;
+    const int valid = moment_tile_rows(q.P, p0);
     cnt += __popcll(rows);
     __syncthreads();                                                             // the previous tile is consumed (and the prologue is written)
     probe_commit<false>(q, M, R, vt, ys, piv, true, false, tid);
@@ -512,7 +485,6 @@ namespace {
 
 int probe_check(const char* what, const float* A, int Ta, int Da, const float* Bs, int Tb, int Db, const float* Y, int Ty, int Cy,
                 const unsigned char* mask, int B, int T, int64_t P, ProbeIn& q) {
-  static thread_local char msg[200];
   const char* why = nullptr;
   if (!A || !Y || !mask) why = "non-null A, Y and mask";
   else if (Da < 1 || Db < 0 || (Db > 0) != (Bs != nullptr)) why = "Da >= 1, and Bs exactly when Db > 0";
@@ -520,16 +492,12 @@ int probe_check(const char* what, const float* A, int Ta, int Da, const float* B
   else if (Cy < 1 || Cy > PROBE_MAX_CY) why = "1 <= Cy <= 16 targets";
   else if (B < 1 || T < 1 || P < 1) why = "B, T, P >= 1";
   else if ((Ta != 1 && Ta != T) || (Db > 0 && Tb != 1 && Tb != T) || (Ty != 1 && Ty != T)) why = "Ta, Tb and Ty each 1 or T";
-  else if (P > 0x7fffffffll || (int64_t)B * T > 0x7fffffffll || (int64_t)B * T * P > 0x7fffffffll) why = "B * T * P < 2^31 observations";
-  if (why) {
-    snprintf(msg, sizeof(msg), "%s: needs %s", what, why);
-    return frl_fail(-2, msg);
-  }
+  else if (!frl_obs_fit(B, T, P)) why = "B * T * P < 2^31 observations";
+  if (why) return frl_failf(-2, "%s: needs %s", what, why);
   q.A = A; q.Bs = Bs; q.Y = Y; q.mask = mask; q.pivot = nullptr;
   q.Ta = Ta; q.Da = Da; q.Tb = Db ? Tb : 1; q.Db = Db; q.Ty = Ty; q.Cy = Cy;
   q.B = B; q.T = T; q.P = (int)P;
-  q.PT = (int)((P + PROBE_ROWS - 1) / PROBE_ROWS);
-  q.ntiles = (int)((int64_t)B * T * q.PT);
+  q.ntiles = frl_moment_tiles(B, T, P, q.PT);
   // rows of whole float4 on 16-byte boundaries in every feature source: the register-prefetch path
   q.fast = (Da & 3) == 0 && ((uintptr_t)A & 15) == 0 && (Db == 0 || ((Db & 3) == 0 && ((uintptr_t)Bs & 15) == 0));
   return 0;
@@ -546,7 +514,7 @@ extern "C" {
 
 // See include/frl_hip.h.
 size_t frl_probe_workspace_bytes(int D, int Cy, int workgroups) {
-  if (D < 1 || D > PROBE_MAX_D || Cy < 1 || Cy > PROBE_MAX_CY || workgroups < 0 || workgroups > PROBE_MAX_WG) return 0;
+  if (D < 1 || D > PROBE_MAX_D || Cy < 1 || Cy > PROBE_MAX_CY || !frl_wg_in_range(workgroups)) return 0;
   const ProbeDims g = probe_dims(D, Cy);
   const size_t Ga = workgroups > 0 ? workgroups : (g.nblk <= 16 ? 1024 : 512), Ge = workgroups > 0 ? workgroups : PROBE_EVAL_WG;
   const size_t acc = probe_align16(8 * Ga) + sizeof(float) * Ga * g.slabF;
@@ -562,12 +530,12 @@ int frl_probe_pivot(const float* A, int Ta, int Da, const float* Bs, int Tb, int
   if (!pivot) return frl_fail(-2, "probe_pivot: null pointer");
   const int C = Da + Db + Cy;
   const size_t need = probe_align16(8 * PROBE_PIVOT_WG) + sizeof(double) * PROBE_PIVOT_WG * (size_t)C;
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < need) return frl_fail(-4, "probe_pivot: workspace too small or not 16-byte aligned");
+  if (int rc = frl_check_workspace("probe_pivot", ws, ws_bytes, need)) return rc;
   long long* cnts = (long long*)ws;
   double* part = (double*)((char*)ws + probe_align16(8 * PROBE_PIVOT_WG));
   const ProbeDims g = probe_dims(Da + Db, Cy);
   const int G = q.ntiles < PROBE_PIVOT_WG ? q.ntiles : PROBE_PIVOT_WG;
-  FRL_LAUNCH(probe_pivot_partial_kernel, dim3((unsigned)G), dim3(256), sizeof(float) * PROBE_ROWS * g.ys, stream, q, g.ys, part, cnts);
+  FRL_LAUNCH(probe_pivot_partial_kernel, dim3((unsigned)G), dim3(256), sizeof(float) * MOMENT_ROWS * g.ys, stream, q, g.ys, part, cnts);
   FRL_LAUNCH(probe_pivot_final_kernel, dim3(1), dim3(1024), 0, stream, (const double*)part, (const long long*)cnts, G, C, pivot);
   return frl_check_launch("probe_pivot");
 }
@@ -577,13 +545,13 @@ int frl_probe_accumulate(const float* A, int Ta, int Da, const float* Bs, int Tb
                          size_t ws_bytes, hipStream_t stream) {
   ProbeIn q;
   if (int rc = probe_check("probe_accumulate", A, Ta, Da, Bs, Tb, Db, Y, Ty, Cy, mask, B, T, P, q)) return rc;
-  if (workgroups < 0 || workgroups > PROBE_MAX_WG) return frl_fail(-2, "probe_accumulate: workgroups must be in 0..4096 (0: the library's choice)");
+  if (int rc = frl_check_workgroups("probe_accumulate", workgroups)) return rc;
   if (!pivot || !S || !n) return frl_fail(-2, "probe_accumulate: null pointer");
   q.pivot = pivot;
   const ProbeDims g = probe_dims(Da + Db, Cy);
   const int G = probe_acc_grid(q.ntiles, g, workgroups);
   const size_t need = probe_align16(8 * (size_t)G) + sizeof(float) * (size_t)G * g.slabF;
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < need) return frl_fail(-4, "probe_accumulate: workspace too small or not 16-byte aligned");
+  if (int rc = frl_check_workspace("probe_accumulate", ws, ws_bytes, need)) return rc;
   long long* cnts = (long long*)ws;
   float* slabs = (float*)((char*)ws + probe_align16(8 * (size_t)G));
   const int NB = (g.nblk + 3) / 4;
@@ -600,16 +568,16 @@ int frl_probe_evaluate(const float* A, int Ta, int Da, const float* Bs, int Tb, 
                        float* pred, void* ws, size_t ws_bytes, hipStream_t stream) {
   ProbeIn q;
   if (int rc = probe_check("probe_evaluate", A, Ta, Da, Bs, Tb, Db, Y, Ty, Cy, mask, B, T, P, q)) return rc;
-  if (workgroups < 0 || workgroups > PROBE_MAX_WG) return frl_fail(-2, "probe_evaluate: workgroups must be in 0..4096 (0: the library's choice)");
+  if (int rc = frl_check_workgroups("probe_evaluate", workgroups)) return rc;
   if (!pivot || !Wc || !bc || !E || !n) return frl_fail(-2, "probe_evaluate: null pointer");
   q.pivot = pivot;
   const int C = Da + Db + Cy, ys = C | 1;
   const int G = probe_eval_grid(q.ntiles, workgroups);
   const size_t need = probe_align16(8 * (size_t)G) + sizeof(double) * (size_t)G * Cy * 3;
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < need) return frl_fail(-4, "probe_evaluate: workspace too small or not 16-byte aligned");
+  if (int rc = frl_check_workspace("probe_evaluate", ws, ws_bytes, need)) return rc;
   long long* cnts = (long long*)ws;
   double* dsl = (double*)((char*)ws + probe_align16(8 * (size_t)G));
-  const size_t lds = sizeof(float) * ((size_t)16 * (Da + Db) + (size_t)PROBE_ROWS * ys + C);
+  const size_t lds = sizeof(float) * ((size_t)16 * (Da + Db) + (size_t)MOMENT_ROWS * ys + C);
   FRL_LAUNCH(probe_eval_kernel, dim3((unsigned)G), dim3(256), lds, stream, q, ys, Wc, bc, dsl, cnts, pred);
   FRL_LAUNCH(probe_eval_reduce_kernel, dim3(1), dim3(1024), 0, stream, (const double*)dsl, (const long long*)cnts, G, Cy, E, (long long*)n);
   return frl_check_launch("probe_evaluate");

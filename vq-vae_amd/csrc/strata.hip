@@ -12,16 +12,14 @@
 // commute: the table is exact whatever the order.
 //
 // frl_strata_moments: per group of a window [g0, g0 + Gc) of the vocabulary and per column, count, S1 = sum y, S2 = sum y^2 of
-// y = x - pivot (and SW, the sum of the per-pixel variances over t, in the temporal mode).  It is gmm_e_kernel's hard pass with the
-// responsibilities given: a workgroup of four waves walks tiles of 64 consecutive pixels in a grid-stride loop, stages y of a tile in
-// LDS, and the waves share out the 16 x 16 blocks of onehot^T [y | y^2 | w] on v_mfma_f32_16x16x4_f32 (exact float32, an fmaf chain
-// in row order; the one-hot operand is formed in registers from the 64 group indices of the tile, y^2 from y) with accumulators in
-// registers for the whole loop.  A tile whose 64 mask bytes are zero, or none of whose pixels falls into the window, is skipped
-// before anything of X is read.  Each workgroup writes one slab; a second kernel adds the slabs in slab order in double.  Counts are
+// y = x - pivot (and SW, the sum of the per-pixel variances over t, in the temporal mode): the staged-tile scheme of frl_moments.hpp over
+// tiles of 64 consecutive pixels, the product being onehot^T [y | y^2 | w] (exact float32, an fmaf chain in row order; the one-hot operand
+// is formed in registers from the 64 group indices of the tile, y^2 from y).  A tile whose 64 mask bytes are zero, or none of whose pixels
+// falls into the window, is skipped before anything of X is read.  The slabs are added in the order of moment_slab_sum.  Counts are
 // integers: an LDS table per workgroup, one 64-bit integer atomic per group.  No float atomics: two runs give the same bits.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
-#include <cstdio>
+#include "frl_moments.hpp"
 
 #define STRATA_MAX_G 4095
 #define STRATA_MAX_R 4096
@@ -30,8 +28,6 @@
 #define STRATA_MAX_GC 128
 #define STRATA_MAX_D 128
 #define STRATA_MAX_GD 8192
-#define STRATA_ROWS 64
-#define STRATA_MAX_WG 4096
 
 namespace {
 
@@ -54,19 +50,16 @@ struct StrataDims {
   size_t lds;
 };
 
-// row stride of the staged tile: the rule of gmm_dims (gmm.hip) and probe_dims (probe.hip)
 StrataDims strata_dims(int Gc, int D, int temporal, int G) {
   StrataDims g;
   g.DB = (D + 15) / 16;
   g.GB = (Gc + 15) / 16;
   g.NQ = temporal ? 3 : 2;
   g.nblk = g.GB * g.NQ * g.DB;
-  int ys = 16 * g.DB;
-  while (ys % 64 != 20 && ys % 64 != 44) ys += 4;
-  g.ys = ys;
+  const int ys = g.ys = frl_tile_stride(16 * g.DB);
   g.slabF = g.nblk * 256;
   // y [64][ys] | w [64][ys] (temporal) | pivot [16 DB] | vocab [G] | group of each row [64] | counts [Gc]
-  g.lds = sizeof(float) * ((size_t)STRATA_ROWS * ys * (temporal ? 2 : 1) + 16 * g.DB) + sizeof(int) * ((size_t)G + STRATA_ROWS + Gc);
+  g.lds = sizeof(float) * ((size_t)MOMENT_ROWS * ys * (temporal ? 2 : 1) + 16 * g.DB) + sizeof(int) * ((size_t)G + MOMENT_ROWS + Gc);
   return g;
 }
 
@@ -206,13 +199,13 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lr = lane & 15, lg = lane >> 4;
   const int D = q.D, ys = q.ys, DB = q.DB, NQ = q.NQ, Gc = q.Gc, G = q.k.G, P = q.k.P, T = q.k.T;
-  const int nblk = ((Gc + 15) >> 4) * NQ * DB, tsz = STRATA_ROWS * ys;
+  const int nblk = ((Gc + 15) >> 4) * NQ * DB, tsz = MOMENT_ROWS * ys;
   float* vt = reinterpret_cast<float*>(smem);                                    // [64][ys]: y
   float* wt = vt + (TEMPORAL ? tsz : 0);                                         // [64][ys]: w
   float* piv = wt + tsz;                                                         // [16 DB]
   int* vl = reinterpret_cast<int*>(piv + 16 * DB);                               // [G]
   int* gl = vl + G;                                                              // [64]: the tile's group in the window, or -1
-  int* cl = gl + STRATA_ROWS;                                                    // [Gc]
+  int* cl = gl + MOMENT_ROWS;                                                    // [Gc]
   for (int d = tid; d < 16 * DB; d += 256) piv[d] = d < D ? q.pivot[d] : 0.f;
   for (int i = tid; i < (TEMPORAL ? 2 : 1) * tsz; i += 256) vt[i] = 0.f;         // the padding columns stay zero
   for (int i = tid; i < G; i += 256) vl[i] = q.k.vocab[i];
@@ -233,10 +226,9 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
   long long unm = 0;
 
   for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
-    const int bt = tile / q.PT, p0 = (tile - bt * q.PT) * STRATA_ROWS;
-    const int b = TEMPORAL ? bt : bt / T, t = TEMPORAL ? 0 : bt - b * T;
-    const int valid = P - p0 < STRATA_ROWS ? P - p0 : STRATA_ROWS;
-    bool on = lane < valid;
+    int b, t, p0;
+    moment_tile(tile, q.PT, TEMPORAL ? 1 : T, b, t, p0);                         // the temporal mode walks (b, p0): t = 0
+    bool on = lane < moment_tile_rows(P, p0);
     if (on && q.k.mask) on = q.k.mask[((size_t)b * q.k.Tm + (q.k.Tm > 1 ? t : 0)) * P + p0 + lane] != 0;
     if (__ballot(on) == 0ull) continue;                                          // uniform: every wave sees the same 64 mask bytes
     int gi = -1, code = 0;
@@ -255,7 +247,7 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
     if (wave == 0) gl[lane] = gi >= 0 ? gi : -1;
     const float* base = q.X + ((size_t)((int64_t)b * T + t) * P + p0) * D;
     if (q.vec) {
-      const int q4 = D >> 2, n4 = STRATA_ROWS * q4;
+      const int q4 = D >> 2, n4 = MOMENT_ROWS * q4;
       for (int e = tid; e < n4; e += 256) {
         const int row = e / q4, c = (e - row * q4) * 4;
         float y[4] = {0.f, 0.f, 0.f, 0.f}, w[4] = {0.f, 0.f, 0.f, 0.f};
@@ -264,7 +256,7 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
         if (TEMPORAL) *reinterpret_cast<f32x4*>(wt + row * ys + c) = f32x4{w[0], w[1], w[2], w[3]};
       }
     } else {
-      const int n = STRATA_ROWS * D;
+      const int n = MOMENT_ROWS * D;
       for (int e = tid; e < n; e += 256) {
         const int row = e / D, c = e - row * D;
         float y[1] = {0.f}, w[1] = {0.f};
@@ -274,16 +266,16 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
       }
     }
     __syncthreads();
-    int gq[STRATA_ROWS / 4];
+    int gq[MOMENT_ROWS / 4];
 #pragma unroll
-    for (int st = 0; st < STRATA_ROWS / 4; ++st) gq[st] = gl[4 * st + lg];
+    for (int st = 0; st < MOMENT_ROWS / 4; ++st) gq[st] = gl[4 * st + lg];
 #pragma unroll
     for (int i = 0; i < NBM; ++i) {
       if (wave + 4 * i < nblk) {
         const float* bp = (kind[i] == 2 ? wt : vt) + boff[i];
         const bool sq = kind[i] == 1;
 #pragma unroll
-        for (int st = 0; st < STRATA_ROWS / 4; ++st) {
+        for (int st = 0; st < MOMENT_ROWS / 4; ++st) {
           float bv = bp[4 * st * ys];
           if (sq) bv *= bv;
           acc[i] = mfma16(gq[st] == gsel[i] ? 1.f : 0.f, bv, acc[i]);
@@ -291,12 +283,7 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
       }
     }
   }
-  float* slab = slabs + (size_t)blockIdx.x * nblk * 256;
-#pragma unroll
-  for (int i = 0; i < NBM; ++i) {
-    const int blk = wave + 4 * i;
-    if (blk < nblk) *reinterpret_cast<f32x4*>(slab + ((size_t)blk * 64 + lane) * 4) = acc[i];
-  }
+  moment_store_slab<NBM>(slabs + (size_t)blockIdx.x * nblk * 256, acc, wave, lane, nblk);
   __syncthreads();
   for (int g = tid; g < Gc; g += 256) {
     const int v = cl[g];
@@ -305,23 +292,19 @@ __global__ __launch_bounds__(256, (NBM <= 4 ? 4 : NBM <= 8 ? 2 : 1)) void strata
   if (tid == 0 && unmatched && unm) atomicAdd(unmatched, (unsigned long long)unm);
 }
 
-// the slabs added in double in slab order, 64 elements x 4 interleaved parts per workgroup, into S1 / S2 / SW [G][D]
+// the slabs added in double (moment_slab_sum), 64 elements per workgroup, into S1 / S2 / SW [G][D]
 __global__ __launch_bounds__(256) void strata_mom_reduce_kernel(const float* __restrict__ slabs, int nslab, int slabF, int DB, int NQ, int D, int g0,
                                                                 int Gc, double* __restrict__ S1, double* __restrict__ S2, double* __restrict__ SW) {
-  __shared__ double part[4][64];
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), p = threadIdx.x >> 6;
-  double s = 0.0;
-#pragma unroll 4
-  for (int g = p; g < nslab; g += 4) s += (double)slabs[(size_t)g * slabF + e];
-  part[p][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (p == 0) {
-    const int blk = e >> 8, l = (e >> 2) & 63, r = e & 3;
+  const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+  const double sum = moment_slab_sum(slabs, nslab, slabF, e, true);
+  if (threadIdx.x < 64) {
+    int blk, row, col;
+    moment_frag_decode(e, blk, row, col);
     const int db = blk % DB, gk = blk / DB, kind = gk % NQ, gb = gk / NQ;
-    const int g = gb * 16 + 4 * (l >> 4) + r, c = db * 16 + (l & 15);
+    const int g = gb * 16 + row, c = db * 16 + col;
     if (g < Gc && c < D) {
       double* out = kind == 0 ? S1 : kind == 1 ? S2 : SW;
-      out[(size_t)(g0 + g) * D + c] += ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+      out[(size_t)(g0 + g) * D + c] += sum;
     }
   }
 }
@@ -333,19 +316,15 @@ namespace {
 
 int strata_check_keys(const char* what, const void* codes, int codes_float, const unsigned char* mask, int Tm, const int32_t* vocab, int G, int B,
                       int T, int64_t P, int workgroups, StrataKeys& k) {
-  static thread_local char msg[200];
   const char* why = nullptr;
   if (!codes || !vocab) why = "non-null codes and vocab";
   else if (codes_float != 0 && codes_float != 1) why = "codes_float 0 (int32) or 1 (float32)";
   else if (G < 1 || G > STRATA_MAX_G) why = "1 <= G <= 4095 codes in the vocabulary";
   else if (B < 1 || T < 1 || P < 1) why = "B, T, P >= 1";
   else if (mask && Tm != 1 && Tm != T) why = "Tm 1 or T";
-  else if (P > 0x7fffffffll || (int64_t)B * T > 0x7fffffffll || (int64_t)B * T * P > 0x7fffffffll) why = "B * T * P < 2^31 observations";
-  else if (workgroups < 0 || workgroups > STRATA_MAX_WG) why = "workgroups in 0..4096 (0: the library's choice)";
-  if (why) {
-    snprintf(msg, sizeof(msg), "%s: needs %s", what, why);
-    return frl_fail(-2, msg);
-  }
+  else if (!frl_obs_fit(B, T, P)) why = "B * T * P < 2^31 observations";
+  else if (!frl_wg_in_range(workgroups)) why = "workgroups in 0..4096 (0: the library's choice)";
+  if (why) return frl_failf(-2, "%s: needs %s", what, why);
   k.codes = codes; k.mask = mask; k.vocab = vocab;
   k.codes_float = codes_float; k.Tm = mask ? Tm : 1; k.G = G; k.B = B; k.T = T; k.P = (int)P;
   return 0;
@@ -375,7 +354,7 @@ extern "C" {
 
 // See include/frl_hip.h.
 size_t frl_strata_workspace_bytes(int Gc, int D, int temporal, int workgroups) {
-  if (Gc < 1 || Gc > STRATA_MAX_GC || D < 1 || D > STRATA_MAX_D || Gc * D > STRATA_MAX_GD || workgroups < 0 || workgroups > STRATA_MAX_WG) return 0;
+  if (Gc < 1 || Gc > STRATA_MAX_GC || D < 1 || D > STRATA_MAX_D || Gc * D > STRATA_MAX_GD || !frl_wg_in_range(workgroups)) return 0;
   // enough for every window of at most Gc groups: a shorter window has smaller slabs but may run more workgroups
   size_t most = 0;
   for (int gc = 1; gc <= Gc; ++gc) {
@@ -421,13 +400,12 @@ int frl_strata_moments(const float* X, const void* codes, int codes_float, const
   if (g.nblk > 128) return frl_fail(-2, "strata_moments: more than 128 blocks of 16 x 16");
   q.X = X; q.pivot = pivot;
   q.D = D; q.DB = g.DB; q.NQ = g.NQ; q.g0 = g0; q.Gc = Gc; q.ys = g.ys;
-  q.PT = (int)((P + STRATA_ROWS - 1) / STRATA_ROWS);
-  q.ntiles = (int)((int64_t)B * (temporal ? 1 : T) * q.PT);
+  q.ntiles = frl_moment_tiles(B, temporal ? 1 : T, P, q.PT);
   q.vec = (D & 3) == 0 && ((uintptr_t)X & 15) == 0;
   const int cap = workgroups > 0 ? workgroups : strata_mom_cap(g);
   const int grid = workgroups > 0 ? workgroups : (q.ntiles < cap ? q.ntiles : cap);
   const size_t need = sizeof(float) * (size_t)grid * g.slabF;
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < need) return frl_fail(-4, "strata_moments: workspace too small or not 16-byte aligned");
+  if (int rc = frl_check_workspace("strata_moments", ws, ws_bytes, need)) return rc;
   float* slabs = (float*)ws;
   unsigned long long* cn = reinterpret_cast<unsigned long long*>(count);
   unsigned long long* um = reinterpret_cast<unsigned long long*>(unmatched);

@@ -201,6 +201,35 @@ def _chk_f32_on(op: str, anchor: str, device, *operands):
             raise ValueError(f"{op}: {name} must be a contiguous float32 {shape} tensor on the device of {anchor}")
 
 
+def _chk_tensor_on(name: str, what: str, t: torch.Tensor, shape, dtype, device):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} {tuple(shape)} tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _chk_one_device(name: str, first: torch.Tensor, *rest):
+    """Every tensor given (None: skipped) lives on the GPU (FrlHipError) and on the device of the first (ValueError)."""
+    for s in (first,) + rest:
+        if s is not None and not s.is_cuda:
+            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+        if s is not None and s.device != first.device:
+            raise ValueError(f"{name}: all tensors must be on one device")
+
+
+MAX_WORKGROUPS = 4096   # gmm.hip, probe.hip, strata.hip: one slab per workgroup, in a workspace the caller owns
+
+
+def chk_workgroups(name: str, workgroups: int, hint: str = " (0: the library's choice)"):
+    if not 0 <= int(workgroups) <= MAX_WORKGROUPS:
+        raise ValueError(f"{name}: workgroups must be in 0..{MAX_WORKGROUPS}{hint}, got {workgroups}")
+
+
+def _owned_workspace(name: str, nbytes, device) -> torch.Tensor:
+    """It carries partial sums from one call to the next: not the shared scratch buffer.  nbytes(lib) is asked once the device is a GPU."""
+    if not torch.device(device).type == "cuda":
+        raise _lib.FrlHipError(f"{name}: the device must be a GPU (no CPU fallback)")
+    return torch.empty(max(nbytes(_lib.load()), 256), dtype=torch.uint8, device=device)
+
+
 def _pair_outputs(b: int, width: int, device):
     """pairstat f32 [B, width], out2 f32 [2], stats f64 [8] of the pair losses (soft neighbourhood, spread ranking)."""
     return (torch.empty(b, width, dtype=torch.float32, device=device), torch.empty(2, dtype=torch.float32, device=device),
@@ -2194,7 +2223,7 @@ def spread_rank_gathered_bwd(emb: torch.Tensor, rows: torch.Tensor, lengths: tor
 # ----------------------------------------------------------------------------------------------
 # diagonal-covariance Gaussian mixtures and the phase summary (csrc/gmm.hip)
 # ----------------------------------------------------------------------------------------------
-GMM_MAX_K, GMM_MAX_D, GMM_MAX_KD, GMM_MAX_WORKGROUPS = 128, 128, 8192, 4096
+GMM_MAX_K, GMM_MAX_D, GMM_MAX_KD, GMM_MAX_WORKGROUPS = 128, 128, 8192, MAX_WORKGROUPS
 GMM_M_EM, GMM_M_LLOYD, GMM_M_INIT = 0, 1, 2
 PHASE_SUMMARY_MAX_T, PHASE_SUMMARY_MAX_D = 64, 64
 
@@ -2224,16 +2253,14 @@ def chk_gmm(x: torch.Tensor, k: int, sample_weight: Optional[torch.Tensor] = Non
     if sample_weight is not None and (sample_weight.dtype != torch.float32 or sample_weight.shape != (x.shape[0],)
                                       or not sample_weight.is_contiguous()):
         raise ValueError(f"{name}: sample_weight must be a contiguous float32 [N] tensor, got {sample_weight.dtype} {tuple(sample_weight.shape)}")
-    if not 0 <= int(workgroups) <= GMM_MAX_WORKGROUPS:
-        raise ValueError(f"{name}: workgroups must be in 0..{GMM_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+    chk_workgroups(name, workgroups)
 
 
 def _chk_gmm_params(name: str, device, k: int, d: int, **tensors):
     for what, (t, shape) in tensors.items():
         if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"{name}: {what} must be a contiguous float32 {shape} tensor, got {t.dtype} {tuple(t.shape)}")
-        if not t.is_cuda:
-            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
+        _chk_one_device(name, t)
         if t.device != device:
             raise ValueError(f"{name}: {what} must be on the device of X")
 
@@ -2241,17 +2268,14 @@ def _chk_gmm_params(name: str, device, k: int, d: int, **tensors):
 def gmm_workspace(n: int, d: int, k: int, device, workgroups: int = 0) -> torch.Tensor:
     """A workspace of one fit: it carries the partial sums from gmm_em_step to gmm_m_step, so it is not the shared scratch buffer."""
     chk_gmm_dims(n, d, k, "gmm_workspace", need_rows=False)
-    if not torch.device(device).type == "cuda":
-        raise _lib.FrlHipError("gmm_workspace: the device must be a GPU (no CPU fallback)")
-    return torch.empty(max(_lib.load().frl_gmm_workspace_bytes(n, d, k, int(workgroups)), 256), dtype=torch.uint8, device=device)
+    return _owned_workspace("gmm_workspace", lambda lib: lib.frl_gmm_workspace_bytes(n, d, k, int(workgroups)), device)
 
 
 @_timed("gmm_pivot")
 def gmm_pivot(x: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
     """X [N, D] f32 -> its column means [D] f32 (summed in double in a fixed order)."""
     chk_gmm(x, 1, name="gmm_pivot", need_rows=False)
-    if not x.is_cuda:
-        raise _lib.FrlHipError("gmm_pivot: tensors must live on the GPU (no CPU fallback)")
+    _chk_one_device("gmm_pivot", x)
     pivot = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
     check(_lib.load().frl_gmm_pivot(_p(x), x.shape[0], x.shape[1], _p(pivot), _p(ws), ws.numel(), _stream()), "frl_gmm_pivot")
     return pivot
@@ -2263,8 +2287,7 @@ def gmm_em_step(x: torch.Tensor, sample_weight: Optional[torch.Tensor], pivot: t
     """The E pass of one iteration (include/frl_hip.h: frl_gmm_em_step): the partial sums land in ws for gmm_m_step.  No host read."""
     k = weights.shape[0] if weights.dim() == 1 else -1
     chk_gmm(x, k, sample_weight, workgroups, "gmm_em_step")
-    if not x.is_cuda:
-        raise _lib.FrlHipError("gmm_em_step: tensors must live on the GPU (no CPU fallback)")
+    _chk_one_device("gmm_em_step", x)
     d = x.shape[1]
     _chk_gmm_params("gmm_em_step", x.device, k, d, pivot=(pivot, (d,)), weights=(weights, (k,)), means_c=(means_c, (k, d)),
                     variances=(variances, (k, d)))
@@ -2282,8 +2305,7 @@ def gmm_m_step(n: int, pivot: torch.Tensor, weights: torch.Tensor, means: torch.
     (float64 [max_iter]) and keeps the iteration count and the convergence flag in `state`.  No host read."""
     k, d = means.shape
     chk_gmm_dims(int(n), d, k, "gmm_m_step")
-    if not 0 <= int(workgroups) <= GMM_MAX_WORKGROUPS:
-        raise ValueError(f"gmm_m_step: workgroups must be in 0..{GMM_MAX_WORKGROUPS}, got {workgroups}")
+    chk_workgroups("gmm_m_step", workgroups, hint="")
     _chk_gmm_params("gmm_m_step", means.device, k, d, pivot=(pivot, (d,)), weights=(weights, (k,)), means=(means, (k, d)),
                     means_c=(means_c, (k, d)), variances=(variances, (k, d)))
     max_iter = 0
@@ -2302,8 +2324,7 @@ def gmm_score(x: torch.Tensor, pivot: torch.Tensor, weights: torch.Tensor, means
     """-> (lse f32 [N], labels int32 [N], resp f32 [N, K] | None) of X under the mixture (include/frl_hip.h: frl_gmm_score)."""
     k = weights.shape[0] if weights.dim() == 1 else -1
     chk_gmm(x, k, name="gmm_score", need_rows=False)
-    if not x.is_cuda:
-        raise _lib.FrlHipError("gmm_score: tensors must live on the GPU (no CPU fallback)")
+    _chk_one_device("gmm_score", x)
     n, d = x.shape
     _chk_gmm_params("gmm_score", x.device, k, d, pivot=(pivot, (d,)), weights=(weights, (k,)), means_c=(means_c, (k, d)),
                     variances=(variances, (k, d)))
@@ -2349,7 +2370,7 @@ def phase_summary(z_phase: torch.Tensor, ysfc: torch.Tensor, low_max: float = 1.
 # ----------------------------------------------------------------------------------------------
 # closed-form linear probes (csrc/probe.hip)
 # ----------------------------------------------------------------------------------------------
-PROBE_MAX_D, PROBE_MAX_CY, PROBE_MAX_WORKGROUPS = 128, 16, 4096
+PROBE_MAX_D, PROBE_MAX_CY, PROBE_MAX_WORKGROUPS = 128, 16, MAX_WORKGROUPS
 
 
 def chk_probe_dims(d: int, cy: int, workgroups: int = 0, name: str = "probe"):
@@ -2358,8 +2379,7 @@ def chk_probe_dims(d: int, cy: int, workgroups: int = 0, name: str = "probe"):
         raise ValueError(f"{name}: supports 1 <= D <= {PROBE_MAX_D} feature columns, got {d}")
     if not 1 <= int(cy) <= PROBE_MAX_CY:
         raise ValueError(f"{name}: supports 1 <= Cy <= {PROBE_MAX_CY} targets, got {cy}")
-    if not 0 <= int(workgroups) <= PROBE_MAX_WORKGROUPS:
-        raise ValueError(f"{name}: workgroups must be in 0..{PROBE_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+    chk_workgroups(name, workgroups)
 
 
 def chk_probe(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor, mask: torch.Tensor, workgroups: int = 0, name: str = "probe"):
@@ -2382,25 +2402,14 @@ def chk_probe(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor, mask
         raise ValueError(f"{name}: empty input, B = {b}, T = {t}, P = {p}, Da = {da}")
     if b * t * p >= 2 ** 31:
         raise ValueError(f"{name}: supports B * T * P < 2^31 observations, got {b * t * p}")
-    for s in (a, bs, y, mask):
-        if s is not None and not s.is_cuda:
-            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
-        if s is not None and s.device != a.device:
-            raise ValueError(f"{name}: all tensors must be on one device")
+    _chk_one_device(name, a, bs, y, mask)
     return b, t, p, da, db, cy
-
-
-def _chk_probe_vec(name: str, what: str, t: torch.Tensor, shape, dtype, device):
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
-        raise ValueError(f"{name}: {what} must be a contiguous {dtype} {tuple(shape)} tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
 
 
 def probe_workspace(d: int, cy: int, device, workgroups: int = 0) -> torch.Tensor:
     """A workspace for the frl_probe_* calls of one probe (slabs of partial sums between a pass and its reduction)."""
     chk_probe_dims(d, cy, workgroups, "probe_workspace")
-    if not torch.device(device).type == "cuda":
-        raise _lib.FrlHipError("probe_workspace: the device must be a GPU (no CPU fallback)")
-    return torch.empty(max(_lib.load().frl_probe_workspace_bytes(int(d), int(cy), int(workgroups)), 256), dtype=torch.uint8, device=device)
+    return _owned_workspace("probe_workspace", lambda lib: lib.frl_probe_workspace_bytes(int(d), int(cy), int(workgroups)), device)
 
 
 def _probe_args(a, bs, y, mask, dims):
@@ -2423,9 +2432,9 @@ def probe_accumulate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tenso
     """S f64 [C+1, C+1] += v^T v, n int64 [1] += the unmasked count (include/frl_hip.h: frl_probe_accumulate).  No host read."""
     dims = chk_probe(a, bs, y, mask, workgroups, "probe_accumulate")
     c = dims[3] + dims[4] + dims[5]
-    _chk_probe_vec("probe_accumulate", "pivot", pivot, (c,), torch.float32, a.device)
-    _chk_probe_vec("probe_accumulate", "S", s, (c + 1, c + 1), torch.float64, a.device)
-    _chk_probe_vec("probe_accumulate", "n", n, (1,), torch.int64, a.device)
+    _chk_tensor_on("probe_accumulate", "pivot", pivot, (c,), torch.float32, a.device)
+    _chk_tensor_on("probe_accumulate", "S", s, (c + 1, c + 1), torch.float64, a.device)
+    _chk_tensor_on("probe_accumulate", "n", n, (1,), torch.int64, a.device)
     check(_lib.load().frl_probe_accumulate(*_probe_args(a, bs, y, mask, dims), _p(pivot), int(workgroups), _p(s), _p(n), _p(ws), ws.numel(),
                                            _stream()), "frl_probe_accumulate")
 
@@ -2437,11 +2446,11 @@ def probe_evaluate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor,
     (include/frl_hip.h: frl_probe_evaluate).  No host read."""
     dims = chk_probe(a, bs, y, mask, workgroups, "probe_evaluate")
     b, t, p, da, db, cy = dims
-    _chk_probe_vec("probe_evaluate", "pivot", pivot, (da + db + cy,), torch.float32, a.device)
-    _chk_probe_vec("probe_evaluate", "Wc", wc, (da + db, cy), torch.float32, a.device)
-    _chk_probe_vec("probe_evaluate", "bc", bc, (cy,), torch.float32, a.device)
-    _chk_probe_vec("probe_evaluate", "E", e, (cy, 3), torch.float64, a.device)
-    _chk_probe_vec("probe_evaluate", "n", n, (1,), torch.int64, a.device)
+    _chk_tensor_on("probe_evaluate", "pivot", pivot, (da + db + cy,), torch.float32, a.device)
+    _chk_tensor_on("probe_evaluate", "Wc", wc, (da + db, cy), torch.float32, a.device)
+    _chk_tensor_on("probe_evaluate", "bc", bc, (cy,), torch.float32, a.device)
+    _chk_tensor_on("probe_evaluate", "E", e, (cy, 3), torch.float64, a.device)
+    _chk_tensor_on("probe_evaluate", "n", n, (1,), torch.int64, a.device)
     pred = torch.empty(b, t, p, cy, dtype=torch.float32, device=a.device) if want_pred else None
     check(_lib.load().frl_probe_evaluate(*_probe_args(a, bs, y, mask, dims), _p(pivot), _p(wc), _p(bc), int(workgroups), _p(e), _p(n), _p(pred),
                                          _p(ws), ws.numel(), _stream()), "frl_probe_evaluate")
@@ -2452,7 +2461,7 @@ def probe_evaluate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor,
 # EVT-stratified diagnostics (csrc/strata.hip)
 # ----------------------------------------------------------------------------------------------
 STRATA_MAX_G, STRATA_MAX_R, STRATA_MAX_CELLS = 4095, 4096, 1 << 24
-STRATA_MAX_GC, STRATA_MAX_D, STRATA_MAX_GD, STRATA_MAX_WORKGROUPS = 128, 128, 8192, 4096
+STRATA_MAX_GC, STRATA_MAX_D, STRATA_MAX_GD, STRATA_MAX_WORKGROUPS = 128, 128, 8192, MAX_WORKGROUPS
 
 
 def chk_strata_table_dims(r: int, g: int, workgroups: int = 0, name: str = "strata_contingency"):
@@ -2463,8 +2472,7 @@ def chk_strata_table_dims(r: int, g: int, workgroups: int = 0, name: str = "stra
         raise ValueError(f"{name}: supports 1 <= R <= {STRATA_MAX_R} row labels, got {r}")
     if int(r) * int(g) > STRATA_MAX_CELLS:
         raise ValueError(f"{name}: supports R * G <= 2^24 cells, got {r} * {g}")
-    if not 0 <= int(workgroups) <= STRATA_MAX_WORKGROUPS:
-        raise ValueError(f"{name}: workgroups must be in 0..{STRATA_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+    chk_workgroups(name, workgroups)
 
 
 def chk_strata_moment_dims(gc: int, d: int, workgroups: int = 0, name: str = "strata_moments"):
@@ -2475,8 +2483,7 @@ def chk_strata_moment_dims(gc: int, d: int, workgroups: int = 0, name: str = "st
         raise ValueError(f"{name}: supports a window of 1 <= Gc <= {STRATA_MAX_GC} groups, got {gc}")
     if int(gc) * int(d) > STRATA_MAX_GD:
         raise ValueError(f"{name}: supports Gc * D <= {STRATA_MAX_GD}, got {gc} * {d}")
-    if not 0 <= int(workgroups) <= STRATA_MAX_WORKGROUPS:
-        raise ValueError(f"{name}: workgroups must be in 0..{STRATA_MAX_WORKGROUPS} (0: the library's choice), got {workgroups}")
+    chk_workgroups(name, workgroups)
 
 
 def _chk_strata_keys(name: str, codes: torch.Tensor, mask: Optional[torch.Tensor], vocab: torch.Tensor, b: int, t: int, p: int):
@@ -2495,21 +2502,10 @@ def _chk_strata_keys(name: str, codes: torch.Tensor, mask: Optional[torch.Tensor
         raise ValueError(f"{name}: supports B * T * P < 2^31 observations, got {b * t * p}")
 
 
-def _chk_strata_device(name: str, first: torch.Tensor, *rest):
-    for s in (first,) + rest:
-        if s is not None and not s.is_cuda:
-            raise _lib.FrlHipError(f"{name}: tensors must live on the GPU (no CPU fallback)")
-        if s is not None and s.device != first.device:
-            raise ValueError(f"{name}: all tensors must be on one device")
-
-
 def strata_workspace(gc: int, d: int, temporal: bool, device, workgroups: int = 0) -> torch.Tensor:
     """A workspace for frl_strata_moments (the slabs of partial sums between the pass and its reduction)."""
     chk_strata_moment_dims(gc, d, workgroups, "strata_workspace")
-    if not torch.device(device).type == "cuda":
-        raise _lib.FrlHipError("strata_workspace: the device must be a GPU (no CPU fallback)")
-    return torch.empty(max(_lib.load().frl_strata_workspace_bytes(int(gc), int(d), int(bool(temporal)), int(workgroups)), 256), dtype=torch.uint8,
-                       device=device)
+    return _owned_workspace("strata_workspace", lambda lib: lib.frl_strata_workspace_bytes(int(gc), int(d), int(bool(temporal)), int(workgroups)), device)
 
 
 @_timed("strata_contingency")
@@ -2529,10 +2525,10 @@ def strata_contingency(rows: torch.Tensor, codes: torch.Tensor, mask: Optional[t
         raise ValueError(f"{name}: table must be [R, G] = [R, {vocab.numel()}], got {tuple(table.shape)}")
     r, g = table.shape
     chk_strata_table_dims(r, g, workgroups, name)
-    _chk_strata_device(name, rows, codes, mask, vocab, table, unmatched, rejected)
-    _chk_probe_vec(name, "table", table, (r, g), torch.int64, rows.device)
-    _chk_probe_vec(name, "unmatched", unmatched, (1,), torch.int64, rows.device)
-    _chk_probe_vec(name, "rejected", rejected, (1,), torch.int64, rows.device)
+    _chk_one_device(name, rows, codes, mask, vocab, table, unmatched, rejected)
+    _chk_tensor_on(name, "table", table, (r, g), torch.int64, rows.device)
+    _chk_tensor_on(name, "unmatched", unmatched, (1,), torch.int64, rows.device)
+    _chk_tensor_on(name, "rejected", rejected, (1,), torch.int64, rows.device)
     check(_lib.load().frl_strata_contingency(_p(rows), tr, _p(codes), int(codes.dtype == torch.float32), _p(mask), 1 if mask is None else mask.shape[1],
                                              _p(vocab), g, b, t, p, r, int(workgroups), _p(table), _p(unmatched), _p(rejected), _stream()),
           "frl_strata_contingency")
@@ -2557,14 +2553,14 @@ def strata_moments(x: torch.Tensor, codes: torch.Tensor, mask: Optional[torch.Te
         raise ValueError(f"{name}: the temporal mode takes a per-pixel mask [B, 1, P], got {tuple(mask.shape)}")
     if temporal and sw is None:
         raise ValueError(f"{name}: the temporal mode needs SW")
-    _chk_strata_device(name, x, codes, mask, vocab, pivot, count, s1, s2, sw, unmatched, ws)
-    _chk_probe_vec(name, "pivot", pivot, (d,), torch.float32, x.device)
-    _chk_probe_vec(name, "count", count, (g,), torch.int64, x.device)
+    _chk_one_device(name, x, codes, mask, vocab, pivot, count, s1, s2, sw, unmatched, ws)
+    _chk_tensor_on(name, "pivot", pivot, (d,), torch.float32, x.device)
+    _chk_tensor_on(name, "count", count, (g,), torch.int64, x.device)
     for what, s in (("S1", s1), ("S2", s2), ("SW", sw)):
         if s is not None:
-            _chk_probe_vec(name, what, s, (g, d), torch.float64, x.device)
+            _chk_tensor_on(name, what, s, (g, d), torch.float64, x.device)
     if unmatched is not None:
-        _chk_probe_vec(name, "unmatched", unmatched, (1,), torch.int64, x.device)
+        _chk_tensor_on(name, "unmatched", unmatched, (1,), torch.int64, x.device)
     check(_lib.load().frl_strata_moments(_p(x), _p(codes), int(codes.dtype == torch.float32), _p(mask), 1 if mask is None else mask.shape[1], _p(vocab),
                                          g, int(g0), int(gc), b, t, p, d, _p(pivot), int(bool(temporal)), int(workgroups), _p(count), _p(s1), _p(s2),
                                          _p(sw), _p(unmatched), _p(ws), ws.numel(), _stream()), "frl_strata_moments")

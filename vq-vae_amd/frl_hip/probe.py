@@ -134,8 +134,7 @@ class RidgeProbe:
     """A streamed closed-form ridge probe; see the module docstring."""
 
     def __init__(self, ridge_lambda: float = 1e-3, standardize: bool = False, workgroups: int = 0):
-        if not 0 <= int(workgroups) <= ops.PROBE_MAX_WORKGROUPS:
-            raise ValueError(f"RidgeProbe: workgroups must be in 0..{ops.PROBE_MAX_WORKGROUPS}, got {workgroups}")
+        ops.chk_workgroups("RidgeProbe", workgroups, hint="")
         self.ridge_lambda, self.standardize, self.workgroups = float(ridge_lambda), bool(standardize), int(workgroups)
         self._S = self._n = self._pivot = self._ws = None                        # device state of the fit
         self._moments = None                                                     # (S, n, pivot) on the host, float64
