@@ -814,6 +814,35 @@ int frl_strata_moments(const float* X, const void* codes, int codes_float, const
                        int Gc, int B, int T, int64_t P, int D, const float* pivot, int temporal, int workgroups, int64_t* count, double* S1,
                        double* S2, double* SW, int64_t* unmatched, void* ws, size_t ws_bytes, frl_stream_t stream);
 
+/* ---- exact grouped quantiles (csrc/quantile.hip) ------------------------------------------------------------------------------------
+ * Exact order statistics of float32 values per cell, by radix select on a monotone key: the quartiles of
+ * frl/training/phase_recovery_curves.py, ysfc_evt_histograms.py, representation/step.py (compute_stats) and data/stats, over every
+ * observation where the reference samples.  key(x) is a uint32 whose unsigned order is the order of x, with -0.0 folded into +0.0 and
+ * every NaN mapped to the largest key.  Four passes of 8-bit digits, most significant first: a pass counts, per (cell, column[, rank]),
+ * the digit of the keys that match the prefix found so far; a small kernel picks the digit that holds the rank.  Integer atomics only
+ * (32-bit, in LDS where the slots of a window fit, else in memory, added once per wave and target): results are exact, bit-identical
+ * from run to run and under any permutation of the input.  Nothing is read back to the host.
+ * frl_quantile_append: keyed as frl_strata_contingency (codes [B][P] against vocab [G], mask [B][Tm][P], rows [B][Tr][P] in [0, R) or
+ * NULL with R = 1; the same order of tests, the same *unmatched and *rejected), R G <= 65535.  X float32 [B][T][P][D], 1 <= D <= 16.  A
+ * surviving observation with a value that is not finite is skipped and *nonfinite += 1; every other one appends a record at a slot taken
+ * from *cursor (int64, one add per workgroup and 1024 observations): cells [capacity] int32 = r G + g, keys [D][capacity] uint32.  Past capacity (< 2^31) nothing is
+ * stored and *dropped += 1 per record.  cursor and the four counters are zeroed by the caller before the first call; calls accumulate.
+ * frl_quantile_select: either the records (cells, keys, capacity, cursor: min(*cursor, capacity) of them, read on the device; X NULL) or
+ * X float32 [N][D] with mask uint8 [N] or NULL, every unmasked row in cell 0 (cells NULL, C = 1, 1 <= N < 2^31).  probs: Q doubles in
+ * [0, 1] on the host.  Per cell of n rows and probability q: v = (n - 1) q in double, k = floor(v), frac [C][Q] (double) = v - k,
+ * lo [C][D][Q] and hi [C][D][Q] (float32) the order statistics of rank k and min(k + 1, n - 1), count [C] (int64) = n.  An empty cell:
+ * count 0, frac 0, lo and hi NaN.  Outputs are overwritten.
+ * Limits: 1 <= D <= 16, 1 <= Q <= 8, 1 <= C <= 65535, C D 2Q <= 2^23, workgroups 0 (the library's choice) or 1..4096: else -2.  Workspace (16-byte
+ * aligned) for frl_quantile_select: frl_quantile_workspace_bytes(C, D, Q) (else -4; 0 beyond the limits); append needs none. */
+size_t frl_quantile_workspace_bytes(int C, int D, int Q);
+int frl_quantile_append(const float* X, const void* codes, int codes_float, const int32_t* rows, int Tr, const unsigned char* mask, int Tm,
+                        const int32_t* vocab, int G, int B, int T, int64_t P, int D, int R, int workgroups, int32_t* cells, uint32_t* keys,
+                        int64_t capacity, int64_t* cursor, int64_t* unmatched, int64_t* rejected, int64_t* nonfinite, int64_t* dropped,
+                        frl_stream_t stream);
+int frl_quantile_select(const int32_t* cells, const uint32_t* keys, int64_t capacity, const int64_t* cursor, const float* X,
+                        const unsigned char* mask, int64_t N, int C, int D, const double* probs, int Q, int workgroups, int64_t* count, float* lo,
+                        float* hi, double* frac, void* ws, size_t ws_bytes, frl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,11 +17,8 @@
 // is formed in registers from the 64 group indices of the tile, y^2 from y).  A tile whose 64 mask bytes are zero, or none of whose pixels
 // falls into the window, is skipped before anything of X is read.  The slabs are added in the order of moment_slab_sum.  Counts are
 // integers: an LDS table per workgroup, one 64-bit integer atomic per group.  No float atomics: two runs give the same bits.
-#include "frl_common.hpp"
-#include "frl_host.hpp"
-#include "frl_moments.hpp"
+#include "strata_keys.hpp"
 
-#define STRATA_MAX_G 4095
 #define STRATA_MAX_R 4096
 #define STRATA_MAX_CELLS (1 << 24)
 #define STRATA_LDS_CELLS 8192
@@ -30,13 +27,6 @@
 #define STRATA_MAX_GD 8192
 
 namespace {
-
-struct StrataKeys {
-  const void* codes;
-  const unsigned char* mask;
-  const int* vocab;
-  int codes_float, Tm, G, B, T, P;
-};
 
 struct StrataMom {
   StrataKeys k;
@@ -66,29 +56,6 @@ StrataDims strata_dims(int Gc, int D, int temporal, int G) {
 int strata_mom_cap(const StrataDims& g) { return g.nblk <= 16 ? 1024 : g.nblk <= 64 ? 512 : 256; }
 
 }  // namespace
-
-// index of `code` in the increasing vl [G], or -1
-__device__ __forceinline__ int strata_find(const int* vl, int G, int code) {
-  int lo = 0, hi = G;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (vl[mid] < code) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < G && vl[lo] == code ? lo : -1;
-}
-
-// the code of pixel i of codes [B P]: false where it is not finite or not > 0; a float is truncated (2^31 and above: INT_MAX)
-__device__ __forceinline__ bool strata_code(const StrataKeys& q, size_t i, int& code) {
-  if (q.codes_float) {
-    const float f = reinterpret_cast<const float*>(q.codes)[i];
-    if (!(f > 0.f) || f == __builtin_inff()) return false;
-    code = f >= 2147483648.f ? 0x7fffffff : (int)f;
-    return true;
-  }
-  code = reinterpret_cast<const int*>(q.codes)[i];
-  return code > 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the contingency table
@@ -313,22 +280,6 @@ __global__ __launch_bounds__(256) void strata_mom_reduce_kernel(const float* __r
 // host
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
-
-int strata_check_keys(const char* what, const void* codes, int codes_float, const unsigned char* mask, int Tm, const int32_t* vocab, int G, int B,
-                      int T, int64_t P, int workgroups, StrataKeys& k) {
-  const char* why = nullptr;
-  if (!codes || !vocab) why = "non-null codes and vocab";
-  else if (codes_float != 0 && codes_float != 1) why = "codes_float 0 (int32) or 1 (float32)";
-  else if (G < 1 || G > STRATA_MAX_G) why = "1 <= G <= 4095 codes in the vocabulary";
-  else if (B < 1 || T < 1 || P < 1) why = "B, T, P >= 1";
-  else if (mask && Tm != 1 && Tm != T) why = "Tm 1 or T";
-  else if (!frl_obs_fit(B, T, P)) why = "B * T * P < 2^31 observations";
-  else if (!frl_wg_in_range(workgroups)) why = "workgroups in 0..4096 (0: the library's choice)";
-  if (why) return frl_failf(-2, "%s: needs %s", what, why);
-  k.codes = codes; k.mask = mask; k.vocab = vocab;
-  k.codes_float = codes_float; k.Tm = mask ? Tm : 1; k.G = G; k.B = B; k.T = T; k.P = (int)P;
-  return 0;
-}
 
 template <bool TEMPORAL>
 int strata_mom_launch(const StrataMom& q, const StrataDims& g, int grid, float* slabs, unsigned long long* count, unsigned long long* unmatched,

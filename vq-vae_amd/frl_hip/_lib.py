@@ -129,6 +129,9 @@ SIGNATURES = {
     "frl_strata_workspace_bytes": (S, [I, I, I, I]),
     "frl_strata_contingency": (c_int, [P, I, P, I, P, I, P, I, I, I, L, I, I, P, P, P, P]),
     "frl_strata_moments": (c_int, [P, P, I, P, I, P, I, I, I, I, I, L, I, P, I, I, P, P, P, P, P, P, S, P]),
+    "frl_quantile_workspace_bytes": (S, [I, I, I]),
+    "frl_quantile_append": (c_int, [P, P, I, P, I, P, I, P, I, I, I, L, I, I, I, P, P, L, P, P, P, P, P, P]),
+    "frl_quantile_select": (c_int, [P, P, L, P, P, P, L, I, I, P, I, I, P, P, P, P, P, S, P]),
     "frl_host_parallel_copy": (c_int, [P, P, S, I]),
     "frl_normalize_chunk_tiles": (c_int, [P, I, I, I, I, I, P, I, I, P, P, I, P, P]),
     "frl_conv3x3_fwd": (c_int, [P, P, P, P, I, I, I, I, I, I, I, P, S, P]),

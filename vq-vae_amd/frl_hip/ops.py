@@ -2564,3 +2564,105 @@ def strata_moments(x: torch.Tensor, codes: torch.Tensor, mask: Optional[torch.Te
     check(_lib.load().frl_strata_moments(_p(x), _p(codes), int(codes.dtype == torch.float32), _p(mask), 1 if mask is None else mask.shape[1], _p(vocab),
                                          g, int(g0), int(gc), b, t, p, d, _p(pivot), int(bool(temporal)), int(workgroups), _p(count), _p(s1), _p(s2),
                                          _p(sw), _p(unmatched), _p(ws), ws.numel(), _stream()), "frl_strata_moments")
+
+
+# ----------------------------------------------------------------------------------------------
+# exact grouped quantiles (csrc/quantile.hip)
+# ----------------------------------------------------------------------------------------------
+QUANT_MAX_D, QUANT_MAX_Q, QUANT_MAX_C, QUANT_MAX_SLOTS = 16, 8, 65535, 1 << 23
+
+
+def chk_quantile_dims(c: int, d: int, q: int = 1, workgroups: int = 0, name: str = "quantile_select"):
+    """The size limits of frl_quantile_append and frl_quantile_select that need no data (ValueError)."""
+    if not 1 <= int(d) <= QUANT_MAX_D:
+        raise ValueError(f"{name}: supports 1 <= D <= {QUANT_MAX_D} columns, got {d}")
+    if not 1 <= int(q) <= QUANT_MAX_Q:
+        raise ValueError(f"{name}: supports 1 <= Q <= {QUANT_MAX_Q} probabilities, got {q}")
+    if not 1 <= int(c) <= QUANT_MAX_C:
+        raise ValueError(f"{name}: supports 1 <= C <= {QUANT_MAX_C} cells, got {c}")
+    if int(c) * int(d) * 2 * int(q) > QUANT_MAX_SLOTS:
+        raise ValueError(f"{name}: supports C * D * 2Q <= 2^23, got {c} * {d} * {2 * int(q)}")
+    chk_workgroups(name, workgroups)
+
+
+def chk_quantile_probs(q, name: str = "quantile_select"):
+    """-> the probabilities as a list of floats: 1 <= Q <= 8 of them, each in [0, 1] (ValueError)."""
+    probs = [float(v) for v in (q if hasattr(q, "__iter__") else [q])]
+    if not 1 <= len(probs) <= QUANT_MAX_Q:
+        raise ValueError(f"{name}: supports 1 <= Q <= {QUANT_MAX_Q} probabilities, got {len(probs)}")
+    if any(not 0.0 <= v <= 1.0 for v in probs):
+        raise ValueError(f"{name}: probabilities must lie in [0, 1], got {probs}")
+    return probs
+
+
+@_timed("quantile_append")
+def quantile_append(x: torch.Tensor, codes: torch.Tensor, rows: Optional[torch.Tensor], mask: Optional[torch.Tensor], vocab: torch.Tensor, r: int,
+                    cells: torch.Tensor, keys: torch.Tensor, state: torch.Tensor, workgroups: int = 0) -> None:
+    """Appends one record (cell, D keys) per surviving observation of x [B, T, P, D] to cells int32 [capacity], keys int32 [D, capacity];
+    state int64 [5] = (cursor, unmatched, rejected, nonfinite, dropped) (include/frl_hip.h: frl_quantile_append).  No host read."""
+    name = "quantile_append"
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be a contiguous float32 [B, T, P, D] tensor, got {x.dtype} {tuple(x.shape)}")
+    b, t, p, d = x.shape
+    _chk_strata_keys(name, codes, mask, vocab, b, t, p)
+    g = vocab.numel()
+    chk_quantile_dims(int(r) * g, d, 1, workgroups, name)
+    if rows is None:
+        if int(r) != 1:
+            raise ValueError(f"{name}: R must be 1 without rows, got {r}")
+    elif rows.dtype != torch.int32 or rows.dim() != 3 or rows.shape[0] != b or rows.shape[2] != p or rows.shape[1] not in (1, t) or not rows.is_contiguous():
+        raise ValueError(f"{name}: rows must be a contiguous int32 [B, Tr, P] = [{b}, 1 or {t}, {p}] tensor, got {rows.dtype} {tuple(rows.shape)}")
+    if cells.dim() != 1 or not 1 <= cells.numel() < 2 ** 31:
+        raise ValueError(f"{name}: cells must be [capacity] with 1 <= capacity < 2^31, got {tuple(cells.shape)}")
+    cap = cells.numel()
+    _chk_one_device(name, x, codes, rows, mask, vocab, cells, keys, state)
+    _chk_tensor_on(name, "cells", cells, (cap,), torch.int32, x.device)
+    _chk_tensor_on(name, "keys", keys, (d, cap), torch.int32, x.device)
+    _chk_tensor_on(name, "state", state, (5,), torch.int64, x.device)
+    sp = state.data_ptr()
+    check(_lib.load().frl_quantile_append(_p(x), _p(codes), int(codes.dtype == torch.float32), _p(rows), 1 if rows is None else rows.shape[1], _p(mask),
+                                          1 if mask is None else mask.shape[1], _p(vocab), g, b, t, p, d, int(r), int(workgroups), _p(cells), _p(keys),
+                                          cap, *[ctypes.c_void_p(sp + 8 * i) for i in range(5)], _stream()), "frl_quantile_append")
+
+
+@_timed("quantile_select")
+def quantile_select(probs, c: int, d: int, cells: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None,
+                    cursor: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, workgroups: int = 0):
+    """The bracketing order statistics of every (cell, column) at every probability, either of the records (cells, keys, cursor) or of the
+    rows of x [N, D] (mask uint8 [N] optional; one cell) -> (count int64 [C], lo f32 [C, D, Q], hi f32 [C, D, Q], frac f64 [C, Q]) on the
+    device (include/frl_hip.h: frl_quantile_select).  No host read."""
+    name = "quantile_select"
+    probs = chk_quantile_probs(probs, name)
+    nq = len(probs)
+    chk_quantile_dims(c, d, nq, workgroups, name)
+    if x is not None:
+        if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] != d or not 1 <= x.shape[0] < 2 ** 31:
+            raise ValueError(f"{name}: x must be a contiguous float32 [N, {d}] tensor with 1 <= N < 2^31, got {x.dtype} {tuple(x.shape)}")
+        if int(c) != 1 or cells is not None or keys is not None or cursor is not None:
+            raise ValueError(f"{name}: x goes into a single cell and excludes records")
+        if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (x.shape[0],) or not mask.is_contiguous()):
+            raise ValueError(f"{name}: mask must be a contiguous uint8 [{x.shape[0]}] tensor, got {mask.dtype} {tuple(mask.shape)}")
+        first, cap, n = x, 0, x.shape[0]
+        _chk_one_device(name, x, mask)
+    else:
+        if cells is None or keys is None or cursor is None or mask is not None:
+            raise ValueError(f"{name}: needs x, or cells, keys and cursor without a mask")
+        first, cap, n = cells, cells.numel(), 0
+        _chk_one_device(name, cells, keys, cursor)
+        _chk_tensor_on(name, "cells", cells, (cap,), torch.int32, cells.device)
+        _chk_tensor_on(name, "keys", keys, (d, cap), torch.int32, cells.device)
+        if cursor.dtype != torch.int64 or cursor.numel() < 1 or not cursor.is_contiguous():
+            raise ValueError(f"{name}: cursor must be a contiguous int64 tensor")
+        if not 1 <= cap < 2 ** 31:
+            raise ValueError(f"{name}: supports 1 <= capacity < 2^31, got {cap}")
+    dev = first.device
+    lib = _lib.load()
+    ws = torch.empty(max(lib.frl_quantile_workspace_bytes(int(c), int(d), nq), 256), dtype=torch.uint8, device=dev)
+    count = torch.empty(int(c), dtype=torch.int64, device=dev)
+    lo = torch.empty(int(c), int(d), nq, dtype=torch.float32, device=dev)
+    hi = torch.empty_like(lo)
+    frac = torch.empty(int(c), nq, dtype=torch.float64, device=dev)
+    pr = (ctypes.c_double * nq)(*probs)
+    check(lib.frl_quantile_select(_p(cells), _p(keys), cap, _p(cursor), _p(x), _p(mask), n, int(c), int(d), ctypes.cast(pr, ctypes.c_void_p), nq,
+                                  int(workgroups), _p(count), _p(lo), _p(hi), _p(frac), _p(ws), ws.numel(), _stream()), "frl_quantile_select")
+    return count, lo, hi, frac

@@ -21,11 +21,15 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["clustering_metrics", "ContingencyTable", "GroupedMoments", "EvtAccumulators", "ysfc_evt_histogram", "YSFC_BINS", "YSFC_BIN_LABELS"]
+__all__ = ["clustering_metrics", "ContingencyTable", "GroupedMoments", "EvtAccumulators", "ysfc_evt_histogram", "YSFC_BINS", "YSFC_BIN_LABELS",
+           "RecoveryCurves", "RECOVERY_YSFC_BINS", "RECOVERY_YSFC_BIN_LABELS"]
 
 # years since fire/change; the right endpoint is exclusive
 YSFC_BINS: List[Tuple[int, int]] = [(0, 1), (1, 2), (2, 3), (3, 5), (5, 8), (8, 13), (13, 20), (20, 31), (31, 41)]
 YSFC_BIN_LABELS: List[str] = ["0", "1", "2", "3–4", "5–7", "8–12", "13–19", "20–30", "31–40"]
+# the 8 bins of phase_recovery_curves.py (it stops at 30 years)
+RECOVERY_YSFC_BINS: List[Tuple[int, int]] = YSFC_BINS[:8]
+RECOVERY_YSFC_BIN_LABELS: List[str] = YSFC_BIN_LABELS[:8]
 
 
 # ---- metrics of a contingency table -------------------------------------------------------------------------------------------------
@@ -488,3 +492,97 @@ class EvtAccumulators:
         ssres = self.probe.sumsq()[i, :c]
         sstot = np.maximum(s2[i, c:] - s1[i, c:] ** 2 / n[i], 1e-12)
         return torch.from_numpy(1.0 - ssres / sstot)
+
+
+# ---- recovery curves ------------------------------------------------------------------------------------------------------------------
+class RecoveryCurves:
+    """phase_recovery_curves.py's `EvtReservoir` and the rows of its `save_csv`, over every observation instead of a reservoir of
+    10 000 per class: per (EVT class, ysfc bin) the quartiles of predicted NBR and the median of observed NBR, exact
+    (quantiles.GroupedQuantiles over the columns [pred_nbr, obs_nbr], one row label per bin).
+
+    An observation counts where its mask is set and 0 <= ysfc <= max_ysfc; one at or beyond the last bin edge (or below the first, with
+    bins that do not start at 0) falls into no bin but still counts in `n_seen`, as in the reference.  `n_seen`, `pixel_counts` and
+    `top_codes` run the select of `table` and keep it, so `top_codes` followed by `table` selects once.  `capacity` is the number of observations the device buffer holds (12 bytes each); `table`
+    raises if more arrived.  Plots, the CSV file and data loading are the caller's."""
+
+    def __init__(self, codes: Sequence[int], bins: Sequence[Tuple[int, int]] = RECOVERY_YSFC_BINS, max_ysfc: float = 30.0, capacity: int = 1 << 22,
+                 labels: Optional[Sequence[str]] = None, workgroups: int = 0):
+        from .quantiles import GroupedQuantiles
+        self.bins = [(float(a), float(b)) for a, b in bins]
+        self._edges = [a for a, _ in self.bins] + [self.bins[-1][1]]
+        if any(self.bins[i][1] != self._edges[i + 1] for i in range(len(self.bins))) or any(a >= b for a, b in zip(self._edges, self._edges[1:])):
+            raise ValueError("RecoveryCurves: bins must be contiguous and increasing")
+        if labels is None:
+            labels = RECOVERY_YSFC_BIN_LABELS if list(bins) == RECOVERY_YSFC_BINS else [f"{a:g}-{b:g}" for a, b in self.bins]
+        if len(labels) != len(self.bins):
+            raise ValueError(f"RecoveryCurves: {len(labels)} labels for {len(self.bins)} bins")
+        self.labels, self.max_ysfc = list(labels), float(max_ysfc)
+        # the last row: outside the bins; counts asked for before table() run table()'s select
+        self._q = GroupedQuantiles(codes, 2, n_rows=len(self.bins) + 1, capacity=capacity, workgroups=workgroups, default_probs=(0.25, 0.5, 0.75))
+        self._index = {c: i for i, c in enumerate(self._q.codes)}
+
+    def add(self, evt_grid: torch.Tensor, ysfc: torch.Tensor, pred_nbr: torch.Tensor, obs_nbr: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
+        """evt_grid [B, ...] (int32 or float32 codes); ysfc, pred_nbr and obs_nbr [B, T, ...]; mask per pixel [B, ...] or per timestep."""
+        name = "RecoveryCurves.add"
+        _need_gpu(name, evt_grid, ysfc, pred_nbr, obs_nbr, mask)
+        _, b, shape = _codes_rows(evt_grid, name)
+        for what, v in (("ysfc", ysfc), ("pred_nbr", pred_nbr), ("obs_nbr", obs_nbr)):
+            if v.dim() != len(shape) + 2 or v.shape[0] != b or tuple(v.shape[2:]) != tuple(shape) or v.shape[1] != ysfc.shape[1]:
+                raise ValueError(f"{name}: {what} must be [B, T, ...] = {(b, 'T') + tuple(shape)}, got {tuple(v.shape)}")
+        t = ysfc.shape[1]
+        y = ysfc.float()
+        keep = (y >= 0) & (y <= self.max_ysfc)
+        if mask is not None:
+            m = mask if mask.dtype == torch.bool else mask != 0
+            keep = keep & (m.unsqueeze(1) if m.dim() == ysfc.dim() - 1 else m)
+        idx = torch.bucketize(y, torch.tensor(self._edges, dtype=torch.float32, device=y.device), right=True) - 1
+        rows = torch.where(keep & (idx >= 0), idx, torch.full_like(idx, len(self.bins))).to(torch.int32)   # below the first edge: no bin either
+        values = torch.stack([pred_nbr.float(), obs_nbr.float()], dim=-1).view(b, t, -1, 1, 2)
+        self._q.partial_fit(values, evt_grid.reshape(b, -1, 1), rows.view(b, t, -1, 1), keep.view(b, t, -1, 1))
+
+    def reset(self) -> None:
+        """Forgets every observation; the device buffer is kept."""
+        self._q.reset()
+
+    @property
+    def unmatched_(self) -> int:
+        return self._q.unmatched_
+
+    @property
+    def nonfinite_(self) -> int:
+        """Counted observations left out because pred_nbr or obs_nbr was not finite."""
+        return self._q.nonfinite_
+
+    @property
+    def dropped_(self) -> int:
+        return self._q.dropped_
+
+    def pixel_counts(self) -> Dict[int, int]:
+        """n_seen per EVT class with an observation (pixel x timestep observations, those beyond the last bin included)."""
+        n = self._q.count_.sum(axis=0)
+        return {c: int(n[i]) for c, i in sorted(self._index.items()) if n[i] > 0}
+
+    def n_seen(self, code: int) -> int:
+        i = self._index.get(int(code))
+        return 0 if i is None else int(self._q.count_[:, i].sum())
+
+    def top_codes(self, k: int) -> List[int]:
+        """The k classes of most observations, descending (the reference's top-K; ties by the lower code)."""
+        return [c for c, _ in sorted(self.pixel_counts().items(), key=lambda cv: (-cv[1], cv[0]))[:int(k)]]
+
+    def table(self, top_codes: Sequence[int]) -> List[dict]:
+        """The rows of the reference's save_csv without evt_name: evt_code, ysfc_bin, n_samples, pred_nbr_q25, pred_nbr_median,
+        pred_nbr_q75, obs_nbr_median per class of top_codes and bin with an observation."""
+        qv = self._q.quantiles([0.25, 0.5, 0.75])                                  # [bins + 1, G, 2, 3]
+        n = self._q.count_
+        rows = []
+        for code in top_codes:
+            i = self._index.get(int(code))
+            if i is None:
+                continue
+            for r, label in enumerate(self.labels):
+                if n[r, i] == 0:
+                    continue
+                rows.append({"evt_code": int(code), "ysfc_bin": label, "n_samples": int(n[r, i]), "pred_nbr_q25": float(qv[r, i, 0, 0]),
+                             "pred_nbr_median": float(qv[r, i, 0, 1]), "pred_nbr_q75": float(qv[r, i, 0, 2]), "obs_nbr_median": float(qv[r, i, 1, 1])})
+        return rows
