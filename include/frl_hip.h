@@ -434,11 +434,27 @@ int frl_vq_prepare(const float* E, int64_t N, int K, int d, int dtype, void* pre
 int frl_vq_assign_fwd_prepared(const void* z, const float* E, void* prep /* NULL: prepare inside the call */, int64_t N, int K, int d,
                                int32_t* idx_out, void* zq_out, float* stats_out, int32_t* counts_out, int dtype, void* ws,
                                size_t ws_bytes, frl_stream_t stream);
+/* As frl_vq_assign_fwd_prepared; stats_copy (NULL or 4 floats): the kernel that writes stats_out stores the same record there too, for a
+ * caller that differentiates its own copy of the statistics (no device-to-device copy behind the call). */
+int frl_vq_assign_fwd_stats2(const void* z, const float* E, void* prep, int64_t N, int K, int d, int32_t* idx_out, void* zq_out,
+                             float* stats_out, float* stats_copy, int32_t* counts_out, int dtype, void* ws, size_t ws_bytes,
+                             frl_stream_t stream);
+/* The prepared image as a job of the weight-image cache `handle`: every frl_pack_cache_refresh(handle) then rewrites `prep` (norms,
+ * fragments, zeroed control block) from E inside its one launch, by the device functions frl_vq_prepare runs -- the same bits.  A caller
+ * that refreshes right behind every codebook update launches no frl_vq_prepare of its own; E and prep outlive the cache, and no
+ * assignment is in flight on the image while the refresh runs.  Registering the same image twice changes nothing. */
+int frl_pack_cache_add_vq(int handle, const float* E, int K, int d, int dtype, void* prep, size_t prep_bytes);
 /* Returns -2 for N, K or d <= 0, for bf16 rows with d > 128 (the widest matrix-core instance covers 128 channels, as the forward), and for
  * float32 rows when one code row (d * 4 bytes) exceeds the 96 KiB LDS chunk. */
 int frl_vq_bwd(const void* g_out, const void* z, const void* zq /* optional */, const float* E, const int32_t* idx, const int32_t* counts,
                const float* gscale, float beta, int64_t N, int K, int d, void* g_z_out, float* g_E_out, float* sums_out,
                int dtype, void* ws, size_t ws_bytes, frl_stream_t stream);
+/* As frl_vq_bwd with the two upstream gradients as two device scalars (g_commit of L_commit, g_codebook of L_codebook) that need not be
+ * adjacent.  NULL means that NO gradient arrives for that term: its factor is formed as coefficient * 0, the bits a zero scalar gives
+ * (a NULL gscale of frl_vq_bwd means {1, 1}).  Deferred: g_codebook stays alive and unchanged until the flush. */
+int frl_vq_bwd_scalars(const void* g_out, const void* z, const void* zq /* optional */, const float* E, const int32_t* idx,
+                       const int32_t* counts, const float* g_commit, const float* g_codebook, float beta, int64_t N, int K, int d,
+                       void* g_z_out, float* g_E_out, float* sums_out, int dtype, void* ws, size_t ws_bytes, frl_stream_t stream);
 /* ok: NULL, or a device float -- ok[0] <= 0 (or NaN) skips the update on the device (the train step's isfinite guard, evaluated
  * without a host synchronisation; frl/training/representation/step.py:1057-1074 "skip the batch"). */
 int frl_vq_ema_update(const float* sums, const int32_t* counts, int K, int d, float decay, float eps, float* ema_count,

@@ -111,11 +111,11 @@ struct WgradEpi {
 // sums themselves (sums_out) feed the EMA update inside the same call, so the job is deferrable only without them; the epilogue READS
 // counts, E and the upstream scale when it runs: a caller that defers keeps those three alive and unchanged until the flush
 struct CodeEpi {
-  const float* E; const int32_t* counts; const float* gscale; float ce_base; int d, bf; float* gE; float* sums_out;
+  const float* E; const int32_t* counts; const float* g_cb; float ce_base; int d, bf; float* gE; float* sums_out;   // g_cb: upstream of L_codebook (null: 1)
   __device__ void operator()(int64_t i, float s) const {
     if (sums_out) sums_out[i] = s;
     if (gE) {
-      const float ce = ce_base * (gscale ? gscale[1] : 1.f);
+      const float ce = ce_base * (g_cb ? g_cb[0] : 1.f);
       const float ev = bf ? (float)(__bf16)E[i] : E[i];
       gE[i] = ce * ((float)counts[i / d] * ev - s);
     }

@@ -12,13 +12,16 @@
 #include <stdint.h>
 #include <stddef.h>
 
-enum { FRL_PACK_PW = 0, FRL_PACK_C3 = 1, FRL_PACK_PW_REP = 2, FRL_PACK_PW_K4 = 3 };
+enum { FRL_PACK_PW = 0, FRL_PACK_C3 = 1, FRL_PACK_PW_REP = 2, FRL_PACK_PW_K4 = 3, FRL_PACK_VQ = 4 };
 
 // One contiguous run of fragments of an image, produced from one float32 weight tensor.
 //   FRL_PACK_PW: pack_weights_lds<T, NF>(dst, W, Cout, Cin, MB, so, si)        (frl_common.hpp)
 //   FRL_PACK_C3: c3_pack_kernel<T, NF>(dst, W, so, si, tap_rev, Cin, Cout)      (conv3x3.hip)
 //   FRL_PACK_PW_REP: as FRL_PACK_PW with the rows of a block replicated over the lane quarters, oc = 4 * mb + (r & 3)
 //   FRL_PACK_PW_K4: as FRL_PACK_PW (NF = 1) with k-element e of lane quarter kc <-> input channel 4 kc + e for e < 4, zero beyond (film_fused.hip)
+//   FRL_PACK_VQ: the prepared codebook image of the quantizer (vq_prepare.hpp), outside the arena: W = the codebook [Cout = K][Cin = d],
+//                dst = the image, so / si = byte offsets of the norms and of the packed fragments inside it (the control block starts it),
+//                MB = kpad, tap_rev = packed fragments; items [0, tap_rev) are fragments, [tap_rev, nfrag) norms.  frl_pack_cache_add_vq (vq.hip)
 struct FrlPackJob {
   const float* W;
   char* dst;             // absolute address once registered; offset inside the image when handed to frl_pack_cached
@@ -46,3 +49,7 @@ static inline FrlPackJob frl_pack_job_c3(const float* W, size_t dst_off, int dty
 // full): the caller packs into its workspace as always.  Otherwise the image's address inside the arena; *hit tells whether it is already
 // packed (skip the prologue) or freshly registered (the caller packs it once, there; later refreshes keep it current).
 void* frl_pack_cached(const FrlPackJob* jobs, int njobs, size_t bytes, bool* hit);
+
+// A job whose destination lies outside the arena (absolute dst) joins the refresh launch of cache `handle`.  Registering the same job
+// again changes nothing.  Returns 0, or a negative code (unknown handle, tables full).
+int frl_pack_cache_add_job(int handle, const FrlPackJob& job);

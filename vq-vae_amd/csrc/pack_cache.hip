@@ -4,12 +4,14 @@
 #include "frl_common.hpp"
 #include "frl_host.hpp"
 #include "frl_pack.hpp"
+#include "vq_prepare.hpp"
 #include <map>
 #include <mutex>
 #include <string.h>
 #include <vector>
 
 #define PK_FRAGS_PER_BLOCK 512
+#define PK_NORMS_PER_BLOCK 256     // FRL_PACK_VQ: a norm item is a serial chain over a code row -- one per thread, not two in a row
 
 // fragment i of a FRL_PACK_PW job: frag index (mb * NF + s) * 64 + lane;  row r of block mb <-> oc = qo*(r>>2) + 4*mb + (r&3);
 // element e of frag s <-> ic = q*kc + s*FE + e  (frl_common.hpp: pack_weights_lds)
@@ -64,17 +66,58 @@ __device__ __forceinline__ void pk_frag_c3(const FrlPackJob& j, int g) {
   }
 }
 
+// item i of a FRL_PACK_VQ job: vq_prepare_kernel's two item kinds (vq_prepare.hpp) with run-time (dtype, NF)
+__device__ __forceinline__ void pk_item_vq(const FrlPackJob& j, int i) {
+  const int K = j.Cout, d = j.Cin, npk = j.tap_rev;
+  if (i >= npk) {
+    float* en = reinterpret_cast<float*>(j.dst + j.so);
+    int* ctl = reinterpret_cast<int*>(j.dst);
+    if (j.dtype == FRL_BF16) vq_prepare_norm<bf16>(j.W, K, d, en, j.MB, ctl, i - npk);
+    else vq_prepare_norm<float>(j.W, K, d, en, j.MB, ctl, i - npk);
+    return;
+  }
+  if (j.dtype == FRL_BF16) {
+    bf16x8* pk = reinterpret_cast<bf16x8*>(j.dst + j.si);
+    switch (j.NF) {
+      case 1: vq_prepare_frag<bf16, 1>(j.W, K, d, pk, i); break;
+      case 2: vq_prepare_frag<bf16, 2>(j.W, K, d, pk, i); break;
+      default: vq_prepare_frag<bf16, 4>(j.W, K, d, pk, i); break;
+    }
+  } else {
+    float* pk = reinterpret_cast<float*>(j.dst + j.si);
+    switch (j.NF) {
+      case 4: vq_prepare_frag<float, 4>(j.W, K, d, pk, i); break;
+      case 8: vq_prepare_frag<float, 8>(j.W, K, d, pk, i); break;
+      case 16: vq_prepare_frag<float, 16>(j.W, K, d, pk, i); break;
+      default: vq_prepare_frag<float, 32>(j.W, K, d, pk, i); break;
+    }
+  }
+}
+
 // blocks[b] = {job index, first fragment of this block inside the job}
 __global__ __launch_bounds__(256) void frl_pack_jobs_kernel(const FrlPackJob* __restrict__ jobs, const int2* __restrict__ blocks) {
   const int2 bk = blocks[blockIdx.x];
   const FrlPackJob j = jobs[bk.x];
-  const int end = (bk.y + PK_FRAGS_PER_BLOCK) < j.nfrag ? (bk.y + PK_FRAGS_PER_BLOCK) : j.nfrag;
+  int span = PK_FRAGS_PER_BLOCK, limit = j.nfrag;
+  if (j.kind == FRL_PACK_VQ) {                               // the fragment blocks end where the norm items begin (pk_blocks_of)
+    if (bk.y >= j.tap_rev) span = PK_NORMS_PER_BLOCK; else limit = j.tap_rev;
+  }
+  const int end = (bk.y + span) < limit ? (bk.y + span) : limit;
   for (int i = bk.y + threadIdx.x; i < end; i += 256) {
-    if (j.kind == FRL_PACK_C3) pk_frag_c3(j, i); else pk_frag_pw(j, i);
+    if (j.kind == FRL_PACK_C3) pk_frag_c3(j, i);
+    else if (j.kind == FRL_PACK_VQ) pk_item_vq(j, i);
+    else pk_frag_pw(j, i);
   }
 }
 
 namespace {
+// first items of the blocks of a job, in the kernel's decomposition
+template <typename F>
+void pk_blocks_of(const FrlPackJob& j, F&& put) {
+  const int nf = j.kind == FRL_PACK_VQ ? j.tap_rev : j.nfrag;
+  for (int f = 0; f < nf; f += PK_FRAGS_PER_BLOCK) put(f);
+  for (int f = nf; f < j.nfrag; f += PK_NORMS_PER_BLOCK) put(f);
+}
 struct Key {
   unsigned char bytes[8 * 72];       // the job list itself (W pointers, shapes, strides, offsets) is the key
   size_t n;
@@ -124,6 +167,23 @@ void* frl_pack_cached(const FrlPackJob* jobs, int njobs, size_t bytes, bool* hit
   c.images[k] = img;
   c.dirty = true;
   return img;
+}
+
+int frl_pack_cache_add_job(int handle, const FrlPackJob& job) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_caches.find(handle);
+  if (it == g_caches.end()) return frl_fail(-2, "pack_cache_add_job: unknown handle");
+  Cache& c = it->second;
+  for (const FrlPackJob& j : c.jobs)
+    if (memcmp(&j, &job, sizeof(FrlPackJob)) == 0) return 0;
+  int nblk = 0;
+  pk_blocks_of(job, [&](int) { ++nblk; });
+  if (c.jobs.size() + 1 > PK_MAX_JOBS || c.blocks.size() + nblk > PK_MAX_BLOCKS) return frl_fail(-4, "pack_cache_add_job: job tables full");
+  const int ji = (int)c.jobs.size();
+  c.jobs.push_back(job);
+  pk_blocks_of(job, [&](int f) { c.blocks.push_back(int2{ji, f}); });
+  c.dirty = true;
+  return 0;
 }
 
 extern "C" {

@@ -26,6 +26,7 @@
 #include "vq_assign_resident.hpp"
 #include "vq_assign_stream.hpp"
 #include "vq_bwd.hpp"
+#include "frl_pack.hpp"
 #include <stdlib.h>
 
 // ---------------------------------------------------------------------------------------------
@@ -119,7 +120,7 @@ static int vq_launch_assign(void (*kern)(P...), int grid, int threads, size_t ld
 }
 template <typename T, int NF>
 static int launch_vq(const void* z, const float* E, char* prep, int64_t N, int K, int d, int32_t* idx, void* zq, float* stats,
-                     int32_t* counts, char* ws, hipStream_t st) {
+                     float* stats_copy, int32_t* counts, char* ws, hipStream_t st) {
   typedef typename DT<T>::frag_t frag_t;
   const VqLayout L = vq_layout(N, K, d);
   const VqPrep P = vq_prep_layout<T, NF>(N, K, d);
@@ -151,7 +152,8 @@ static int launch_vq(const void* z, const float* E, char* prep, int64_t N, int K
       if (lds > 160 * 1024) return frl_fail(-3, "vq_assign: LDS budget exceeded");
       const auto kern = nt == 4 ? vq_assign_stream_kernel<4> : nt == 2 ? vq_assign_stream_kernel<2> : vq_assign_stream_kernel<1>;
       const int rc = vq_launch_assign(kern, grid_s, 64 * VQS_NW, lds, st, (const bf16*)z, en, N, K, Kc, idx, (bf16*)zq, (float*)(ws + L.partial),
-                                      (const bf16x8*)pk, (VqCtl*)(prep + P.ctl), counts, stats, (unsigned*)(ws + L.amb), (float*)(ws + L.amb_lim));
+                                      (const bf16x8*)pk, (VqCtl*)(prep + P.ctl), counts, stats, (unsigned*)(ws + L.amb), (float*)(ws + L.amb_lim),
+                                      stats_copy);
       return rc ? rc : frl_check_launch("vq_assign");
     }
   }
@@ -171,7 +173,7 @@ static int launch_vq(const void* z, const float* E, char* prep, int64_t N, int K
       if (nwr == 8) kern = vq_assign_resident_kernel<T, NF, VQ_RES_NT, 8>;
     }
     const int rc = vq_launch_assign(kern, grid_r, 64 * nwr, lds, st, (const T*)z, E, en, N, K, d, Kc, idx, (T*)zq, (float*)(ws + L.partial), pk,
-                                    (VqCtl*)(prep + P.ctl), counts, stats);
+                                    (VqCtl*)(prep + P.ctl), counts, stats, stats_copy);
     return rc ? rc : frl_check_launch("vq_assign");
   }
   // multi-chunk: two half-size chunk buffers (fragments + norms each), so that two workgroups still fit a CU
@@ -185,7 +187,7 @@ static int launch_vq(const void* z, const float* E, char* prep, int64_t N, int K
   FRL_LAUNCH_AS("vq_fixup_tile_kernel", (vq_fixup_tile_kernel<T, NF>), dim3(1024), dim3(64 * VQ_FIXT_WAVES), 0, st, (const T*)z, E, en, pk, K, P.kpad, d,
                 (const int32_t*)(ws + L.amb), (const float*)(ws + L.amb_lim), hdr, idx, (T*)zq, (int32_t*)(ws + L.counts_fix));
   FRL_LAUNCH(vq_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)(ws + L.partial), L.grid * nw, (const VqHeader*)hdr,
-             (const int32_t*)(ws + L.counts_fix), counts, K, N, d, stats);
+             (const int32_t*)(ws + L.counts_fix), counts, K, N, d, stats, stats_copy);
   return frl_check_launch("vq_assign");
 }
 
@@ -193,6 +195,57 @@ static int vq_bwd_chunk(int K, int d) {
   int kc = K;
   while ((size_t)kc * d * 4 > 96 * 1024 && kc > 1) kc = (kc + 1) / 2;
   return kc;
+}
+
+// frl_vq_bwd and frl_vq_bwd_scalars: g_cm / g_cb = device scalars, the upstream gradients of L_commit / L_codebook (null: 1), on top of
+// the host factors cz_factor / ce_factor (0 for a term that receives no gradient: its coefficient is then formed as c * 0)
+extern "C" size_t frl_vq_workspace_bytes(int64_t N, int K, int d);
+static int vq_bwd_impl(const void* g_out, const void* z, const void* zq, const float* E, const int32_t* idx, const int32_t* counts,
+                       const float* g_cm, const float* g_cb, float cz_factor, float ce_factor, float beta, int64_t N, int K, int d, void* g_z_out,
+                       float* g_E_out, float* sums_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
+  if (N <= 0 || K <= 0 || d <= 0) return frl_fail(-2, "vq_bwd: empty input");
+  if (dtype != FRL_F32 && dtype != FRL_BF16) return frl_fail(-2, "vq_bwd: bad dtype");
+  // the widest matrix-core instance covers 128 channels (as the forward); the float32 kernel is generic in d up to one code per LDS chunk
+  if (dtype == FRL_BF16 && d > 128) return frl_fail(-2, "vq_bwd: d > 128 unsupported in bf16");
+  if (ws_bytes < frl_vq_workspace_bytes(N, K, d)) return frl_fail(-4, "vq_bwd: workspace too small");
+  const int Kc = vq_bwd_chunk(K, d);
+  const size_t lds = (size_t)Kc * d * 4;
+  if (dtype == FRL_F32 && lds > 96 * 1024) return frl_fail(-2, "vq_bwd: one code row exceeds the LDS chunk");
+  const int64_t rows = (N + VQ_BWD_WGS - 1) / VQ_BWD_WGS;
+  const float cz = beta * 2.f / ((float)N * (float)d) * cz_factor, ce = 2.f / ((float)N * (float)d) * ce_factor;
+  float* slab = (float*)ws;
+  if (dtype == FRL_F32) {
+    auto kern = vq_bwd_kernel<float>;
+    if (lds > 64 * 1024) FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FRL_LAUNCH_AS("vq_bwd_kernel", kern, dim3(VQ_BWD_WGS), dim3(256), lds, stream, (const float*)g_out, (const float*)z, E, idx, g_cm,
+                       cz, N, K, d, Kc, rows, (float*)g_z_out, slab);
+    launch_slab_reduce_deferrable<float, CodeEpi>((const float*)slab, VQ_BWD_WGS, (int64_t)K * d, CodeEpi{E, counts, g_cb, ce, d, 0, g_E_out, sums_out}, stream, sums_out == nullptr);
+  } else if (dtype == FRL_BF16) {
+    const int64_t rows64 = (rows + 63) / 64 * 64;
+    if (d <= 32) {
+      FRL_LAUNCH((vq_bwd_mfma_kernel<4, 2, 8>), dim3(VQ_BWD_WGS), dim3(512), (size_t)64 * 40 * 2 + 256, stream, (const bf16*)g_out, (const bf16*)z, (const bf16*)zq, E, idx,
+                 g_cm, cz, N, K, d, rows64, (bf16*)g_z_out, slab);
+    } else if (d <= 64) {
+      FRL_LAUNCH((vq_bwd_mfma_kernel<4, 4, 8>), dim3(VQ_BWD_WGS), dim3(512), (size_t)64 * 72 * 2 + 256, stream, (const bf16*)g_out, (const bf16*)z, (const bf16*)zq, E, idx,
+                 g_cm, cz, N, K, d, rows64, (bf16*)g_z_out, slab);
+    } else {
+      FRL_LAUNCH((vq_bwd_mfma_kernel<2, 8, 8>), dim3(VQ_BWD_WGS), dim3(512), (size_t)64 * 136 * 2 + 256, stream, (const bf16*)g_out, (const bf16*)z, (const bf16*)zq, E, idx,
+                 g_cm, cz, N, K, d, rows64, (bf16*)g_z_out, slab);
+    }
+    launch_slab_reduce_deferrable<float, CodeEpi>((const float*)slab, VQ_BWD_WGS, (int64_t)K * d, CodeEpi{E, counts, g_cb, ce, d, 1, g_E_out, sums_out}, stream, sums_out == nullptr);
+  } else return frl_fail(-2, "vq_bwd: bad dtype");
+  return frl_check_launch("vq_bwd");
+}
+
+// the prepared image as a FRL_PACK_VQ job (frl_pack.hpp) of a weight-image cache: see frl_pack_cache_add_vq
+template <typename T, int NF>
+static int vq_pack_job(int handle, const float* E, int K, int d, int dtype, char* prep) {
+  const VqPrep P = vq_prep_layout<T, NF>(0, K, d);
+  const int kz = P.kpad > 64 ? P.kpad : 64;
+  FrlPackJob j;
+  j.W = E; j.dst = prep; j.so = (long long)P.en; j.si = (long long)P.pack; j.kind = FRL_PACK_VQ; j.dtype = dtype; j.NF = NF;
+  j.Cout = K; j.Cin = d; j.MB = P.kpad; j.tap_rev = P.npk; j.nfrag = P.npk + kz;
+  return frl_pack_cache_add_job(handle, j);
 }
 
 extern "C" {
@@ -242,19 +295,37 @@ int frl_vq_prepare(const float* E, int64_t N, int K, int d, int dtype, void* pre
 #undef VQ_CALL_PREP
 }
 
+// The image as a job of a weight-image cache's refresh launch (frl_pack.hpp: FRL_PACK_VQ): frl_pack_cache_refresh(handle) then rewrites
+// `prep` from E -- norms, fragments and the zeroed control block, by vq_prepare_kernel's own device functions -- together with the weight
+// images, and a caller that refreshes right behind every codebook update needs no frl_vq_prepare launch of its own.  E and prep must
+// outlive the cache; no assignment may be in flight on the image when the refresh runs.
+int frl_pack_cache_add_vq(int handle, const float* E, int K, int d, int dtype, void* prep, size_t prep_bytes) {
+  if (K <= 0 || d <= 0 || d > 128 || E == nullptr) return frl_fail(-2, "pack_cache_add_vq: bad codebook shape");
+  if (prep == nullptr || prep_bytes < frl_vq_prepared_bytes(K, d)) return frl_fail(-4, "pack_cache_add_vq: buffer too small");
+#define VQ_CALL_JOB(T_, NF_) vq_pack_job<T_, NF_>(handle, E, K, d, dtype, (char*)prep)
+  VQ_DISPATCH(dtype, d, VQ_CALL_JOB);
+#undef VQ_CALL_JOB
+}
+
 // z [N][d] (dtype), E [K][d] f32 master codebook.  Outputs: idx_out [N] int32, zq_out [N][d] (dtype, the
 // codebook rows rounded to dtype), stats_out [4] f32 = {sum ||z - z_q||^2, perplexity, #rows re-evaluated in
 // float64, mean squared error = sum / (N d)}, counts_out [K] int32 code usage.  In bf16 mode distances are taken to the bf16-rounded codebook.
 // prep: NULL, or the image frl_vq_prepare wrote for THIS codebook content, dtype and row count class.  The image carries the kernel's
 // arrival counter and histogram accumulator (zeroed by frl_vq_prepare, left zeroed by every call): one call in flight per image.
-int frl_vq_assign_fwd_prepared(const void* z, const float* E, void* prep, int64_t N, int K, int d, int32_t* idx_out, void* zq_out,
-                               float* stats_out, int32_t* counts_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
+// stats_copy (optional, [4] f32): the kernel that writes stats_out stores the record there as well.
+int frl_vq_assign_fwd_stats2(const void* z, const float* E, void* prep, int64_t N, int K, int d, int32_t* idx_out, void* zq_out,
+                             float* stats_out, float* stats_copy, int32_t* counts_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (N <= 0 || K <= 0 || d <= 0) return frl_fail(-2, "vq_assign: empty input");
   if (d > 128) return frl_fail(-2, "vq_assign: d > 128 unsupported");
   if (ws_bytes < frl_vq_workspace_bytes(N, K, d)) return frl_fail(-4, "vq_assign: workspace too small");
-#define VQ_CALL_FWD(T_, NF_) launch_vq<T_, NF_>(z, E, (char*)prep, N, K, d, idx_out, zq_out, stats_out, counts_out, (char*)ws, stream)
+#define VQ_CALL_FWD(T_, NF_) launch_vq<T_, NF_>(z, E, (char*)prep, N, K, d, idx_out, zq_out, stats_out, stats_copy, counts_out, (char*)ws, stream)
   VQ_DISPATCH(dtype, d, VQ_CALL_FWD);
 #undef VQ_CALL_FWD
+}
+
+int frl_vq_assign_fwd_prepared(const void* z, const float* E, void* prep, int64_t N, int K, int d, int32_t* idx_out, void* zq_out,
+                               float* stats_out, int32_t* counts_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return frl_vq_assign_fwd_stats2(z, E, prep, N, K, d, idx_out, zq_out, stats_out, nullptr, counts_out, dtype, ws, ws_bytes, stream);
 }
 
 int frl_vq_assign_fwd(const void* z, const float* E, int64_t N, int K, int d, int32_t* idx_out, void* zq_out,
@@ -266,41 +337,20 @@ int frl_vq_assign_fwd(const void* z, const float* E, int64_t N, int K, int d, in
 // gscale: device float[2] = upstream gradients of {L_commit, L_codebook}, may be null (= {1, 1}).
 // zq (optional): the forward's z_q rows; when given the bf16 path reads it instead of gathering codebook rows.  g_out may be null (=0).
 // g_z / g_E may be null to skip.  sums_out (optional, [K][d] f32) receives the per-code sums of z.
+// frl_vq_bwd_scalars: the two upstream gradients as two device scalars, g_commit for L_commit and g_codebook for L_codebook; a null one
+// means NO gradient arrives for that term (its factor is cz * 0 or ce * 0, the bits a zero scalar gives) -- not 1 as a null gscale does.
 int frl_vq_bwd(const void* g_out, const void* z, const void* zq, const float* E, const int32_t* idx, const int32_t* counts,
                const float* gscale, float beta, int64_t N, int K, int d, void* g_z_out, float* g_E_out,
                float* sums_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
-  if (N <= 0 || K <= 0 || d <= 0) return frl_fail(-2, "vq_bwd: empty input");
-  if (dtype != FRL_F32 && dtype != FRL_BF16) return frl_fail(-2, "vq_bwd: bad dtype");
-  // the widest matrix-core instance covers 128 channels (as the forward); the float32 kernel is generic in d up to one code per LDS chunk
-  if (dtype == FRL_BF16 && d > 128) return frl_fail(-2, "vq_bwd: d > 128 unsupported in bf16");
-  if (ws_bytes < frl_vq_workspace_bytes(N, K, d)) return frl_fail(-4, "vq_bwd: workspace too small");
-  const int Kc = vq_bwd_chunk(K, d);
-  const size_t lds = (size_t)Kc * d * 4;
-  if (dtype == FRL_F32 && lds > 96 * 1024) return frl_fail(-2, "vq_bwd: one code row exceeds the LDS chunk");
-  const int64_t rows = (N + VQ_BWD_WGS - 1) / VQ_BWD_WGS;
-  const float cz = beta * 2.f / ((float)N * (float)d), ce = 2.f / ((float)N * (float)d);
-  float* slab = (float*)ws;
-  if (dtype == FRL_F32) {
-    auto kern = vq_bwd_kernel<float>;
-    if (lds > 64 * 1024) FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    FRL_LAUNCH_AS("vq_bwd_kernel", kern, dim3(VQ_BWD_WGS), dim3(256), lds, stream, (const float*)g_out, (const float*)z, E, idx, gscale,
-                       cz, N, K, d, Kc, rows, (float*)g_z_out, slab);
-    launch_slab_reduce_deferrable<float, CodeEpi>((const float*)slab, VQ_BWD_WGS, (int64_t)K * d, CodeEpi{E, counts, gscale, ce, d, 0, g_E_out, sums_out}, stream, sums_out == nullptr);
-  } else if (dtype == FRL_BF16) {
-    const int64_t rows64 = (rows + 63) / 64 * 64;
-    if (d <= 32) {
-      FRL_LAUNCH((vq_bwd_mfma_kernel<4, 2, 8>), dim3(VQ_BWD_WGS), dim3(512), (size_t)64 * 40 * 2 + 256, stream, (const bf16*)g_out, (const bf16*)z, (const bf16*)zq, E, idx,
-                 gscale, cz, N, K, d, rows64, (bf16*)g_z_out, slab);
-    } else if (d <= 64) {
-      FRL_LAUNCH((vq_bwd_mfma_kernel<4, 4, 8>), dim3(VQ_BWD_WGS), dim3(512), (size_t)64 * 72 * 2 + 256, stream, (const bf16*)g_out, (const bf16*)z, (const bf16*)zq, E, idx,
-                 gscale, cz, N, K, d, rows64, (bf16*)g_z_out, slab);
-    } else {
-      FRL_LAUNCH((vq_bwd_mfma_kernel<2, 8, 8>), dim3(VQ_BWD_WGS), dim3(512), (size_t)64 * 136 * 2 + 256, stream, (const bf16*)g_out, (const bf16*)z, (const bf16*)zq, E, idx,
-                 gscale, cz, N, K, d, rows64, (bf16*)g_z_out, slab);
-    }
-    launch_slab_reduce_deferrable<float, CodeEpi>((const float*)slab, VQ_BWD_WGS, (int64_t)K * d, CodeEpi{E, counts, gscale, ce, d, 1, g_E_out, sums_out}, stream, sums_out == nullptr);
-  } else return frl_fail(-2, "vq_bwd: bad dtype");
-  return frl_check_launch("vq_bwd");
+  return vq_bwd_impl(g_out, z, zq, E, idx, counts, gscale, gscale ? gscale + 1 : nullptr, 1.f, 1.f, beta, N, K, d, g_z_out, g_E_out, sums_out, dtype,
+                     ws, ws_bytes, stream);
+}
+
+int frl_vq_bwd_scalars(const void* g_out, const void* z, const void* zq, const float* E, const int32_t* idx, const int32_t* counts,
+                       const float* g_commit, const float* g_codebook, float beta, int64_t N, int K, int d, void* g_z_out, float* g_E_out,
+                       float* sums_out, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return vq_bwd_impl(g_out, z, zq, E, idx, counts, g_commit, g_codebook, g_commit ? 1.f : 0.f, g_codebook ? 1.f : 0.f, beta, N, K, d, g_z_out,
+                     g_E_out, sums_out, dtype, ws, ws_bytes, stream);
 }
 
 // EMA codebook update from this batch's assignments: counts [K] int32 and per-code sums [K][d] f32

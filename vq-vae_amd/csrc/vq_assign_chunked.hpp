@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * VQ_FIXT_WAVES) void vq_fixup_tile_kernel(const
 // stats = {sqerr_sum, perplexity, n_re-evaluated, 0}
 __global__ __launch_bounds__(256) void vq_finalize_kernel(const float* __restrict__ partial, int npartial, const VqHeader* __restrict__ hdr,
                                                           const int32_t* __restrict__ counts_acc, int32_t* __restrict__ counts, int K, int64_t N,
-                                                          int d, float* __restrict__ stats) {
+                                                          int d, float* __restrict__ stats, float* __restrict__ stats_copy /*[4] or null*/) {
   __shared__ double red[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < npartial; i += 256) s += (double)partial[i];
@@ -311,5 +311,8 @@ __global__ __launch_bounds__(256) void vq_finalize_kernel(const float* __restric
     stats[1] = (float)exp(-red[0]);
     stats[2] = (float)hdr->namb;
     stats[3] = (float)(sq / ((double)N * (double)d));
+    if (stats_copy) {
+      for (int i = 0; i < 4; ++i) stats_copy[i] = stats[i];
+    }
   }
 }

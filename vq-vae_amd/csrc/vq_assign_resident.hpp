@@ -26,7 +26,8 @@ template <typename T, int NF, int NT, int NW>
 __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : 1)) void vq_assign_resident_kernel(
     const T* __restrict__ Z, const float* __restrict__ E, const float* __restrict__ en_g, int64_t N, int K, int d, int Kc,
     int32_t* __restrict__ idx_out, T* __restrict__ zq_out, float* __restrict__ partial /*[grid*NW]*/,
-    const typename DT<T>::frag_t* __restrict__ pk, VqCtl* __restrict__ ctl, int32_t* __restrict__ counts_out, float* __restrict__ stats_out) {
+    const typename DT<T>::frag_t* __restrict__ pk, VqCtl* __restrict__ ctl, int32_t* __restrict__ counts_out, float* __restrict__ stats_out,
+    float* __restrict__ stats_copy /*[4] or null*/) {
   typedef typename DT<T>::frag_t frag_t;
   constexpr int FE = DT<T>::FE;
   constexpr int q = NF * FE;                 // channels per lane quarter
@@ -411,7 +412,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : 1)) void vq_assign_resident
   const bool last = misc[17] != 0;
   __syncthreads();                                                  // (red below may overlap misc when the image is tiny)
   // (smem: the codebook fragments are no longer needed)
-  if (last) vq_fold_stats<NW>(reinterpret_cast<double*>(smem), tidt, tidt & 63, tidt >> 6, partial, (int)gridDim.x * NW, ctl, K, N, d, counts_out, stats_out);
+  if (last) vq_fold_stats<NW>(reinterpret_cast<double*>(smem), tidt, tidt & 63, tidt >> 6, partial, (int)gridDim.x * NW, ctl, K, N, d, counts_out, stats_out, stats_copy);
 #ifdef VQ_STAMPS
   VQ_ST(6);                                                        // partials, histogram atomics, ticket, (last workgroup) statistics
   __syncthreads();

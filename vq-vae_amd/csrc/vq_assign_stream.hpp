@@ -128,7 +128,8 @@ template <int NT>
 __global__ __launch_bounds__(VQS_NW * 64, 1) void vq_assign_stream_kernel(
     const bf16* __restrict__ Z, const float* __restrict__ en_g, int64_t N, int K, int Kc, int32_t* __restrict__ idx_out,
     bf16* __restrict__ zq_out, float* __restrict__ partial /*[grid*NW]*/, const bf16x8* __restrict__ pk, VqCtl* __restrict__ ctl,
-    int32_t* __restrict__ counts_out, float* __restrict__ stats_out, unsigned* __restrict__ ovf_row /*[N]*/, float* __restrict__ ovf_lim /*[N]*/) {
+    int32_t* __restrict__ counts_out, float* __restrict__ stats_out, unsigned* __restrict__ ovf_row /*[N]*/, float* __restrict__ ovf_lim /*[N]*/,
+    float* __restrict__ stats_copy /*[4] or null*/) {
   constexpr int NF = 2, q = 16, d = 64, NW = VQS_NW;
   constexpr int BATCH = NW * NT * 16;
   static_assert(NW * VQS_CAP <= VQ_FAST_ROWS, "parked rows of a workgroup");
@@ -484,7 +485,7 @@ __global__ __launch_bounds__(VQS_NW * 64, 1) void vq_assign_stream_kernel(
   const bool last = misc[17] != 0;
   __syncthreads();
   // (smem: the codebook fragments are no longer needed)
-  if (last) vq_fold_stats<NW>(reinterpret_cast<double*>(smem), tid, lane, wave, partial, (int)gridDim.x * NW, ctl, K, N, d, counts_out, stats_out);
+  if (last) vq_fold_stats<NW>(reinterpret_cast<double*>(smem), tid, lane, wave, partial, (int)gridDim.x * NW, ctl, K, N, d, counts_out, stats_out, stats_copy);
 #ifdef VQ_STAMPS
   VQ_ST(6);                                                        // partials, histogram atomics, ticket, (last workgroup) statistics
   __syncthreads();

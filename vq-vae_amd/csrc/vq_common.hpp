@@ -208,11 +208,11 @@ __device__ __forceinline__ void vq_flush_hist(const int* __restrict__ hist, int3
 // of the squared error and p log p of the histogram are summed in double -- thread i takes the entries i, i + 64 NW, .. in that order,
 // wave_sum_d, then thread 0 adds the wave sums in wave order -- so stats do not depend on which workgroup folds.  lane / wave are those
 // of tid (passed in: the callers hold them already).  Writes counts_out and
-// stats_out = {sum ||z - z_q||^2, perplexity, rows re-evaluated, mean squared error} and re-arms the control block (histogram
+// stats_out = {sum ||z - z_q||^2, perplexity, rows re-evaluated, mean squared error} (and the same four floats to stats_copy when given) and re-arms the control block (histogram
 // accumulator, namb, done) for the next call.  red: 2 NW doubles of LDS.
 template <int NW>
 __device__ __forceinline__ void vq_fold_stats(double* red, int tid, int lane, int wave, const float* partial, int npartial, VqCtl* ctl, int K, int64_t N, int d,
-                                              int32_t* __restrict__ counts_out, float* __restrict__ stats_out) {
+                                              int32_t* __restrict__ counts_out, float* __restrict__ stats_out, float* __restrict__ stats_copy) {
   int32_t* counts_acc = reinterpret_cast<int32_t*>(ctl + 1);
   double sp = 0.0;
   for (int i = tid; i < npartial; i += NW * 64) sp += (double)__hip_atomic_load(&partial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -230,10 +230,14 @@ __device__ __forceinline__ void vq_fold_stats(double* red, int tid, int lane, in
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < NW; ++w) { red[0] += red[w]; red[NW] += red[NW + w]; }     // fixed order
-    stats_out[0] = (float)red[0];
-    stats_out[1] = (float)exp(-red[NW]);
-    stats_out[2] = (float)__hip_atomic_load(&ctl->namb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    stats_out[3] = (float)(red[0] / ((double)N * (double)d));   // mean squared error (the two VQ loss terms)
+    const float st[4] = {(float)red[0], (float)exp(-red[NW]), (float)__hip_atomic_load(&ctl->namb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                         (float)(red[0] / ((double)N * (double)d))};   // [3]: mean squared error (the two VQ loss terms)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) stats_out[i] = st[i];
+    if (stats_copy) {                                            // the record a second time, for a caller that differentiates its own copy
+#pragma unroll
+      for (int i = 0; i < 4; ++i) stats_copy[i] = st[i];
+    }
     __hip_atomic_store(&ctl->namb, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&ctl->done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

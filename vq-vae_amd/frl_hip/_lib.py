@@ -54,7 +54,10 @@ SIGNATURES = {
     "frl_vq_prepare": (c_int, [P, L, I, I, I, P, S, P]),
     "frl_vq_stream_tiles": (c_int, [I]),
     "frl_vq_assign_fwd_prepared": (c_int, [P, P, P, L, I, I, P, P, P, P, I, P, S, P]),
+    "frl_vq_assign_fwd_stats2": (c_int, [P, P, P, L, I, I, P, P, P, P, P, I, P, S, P]),
+    "frl_pack_cache_add_vq": (c_int, [I, P, I, I, I, P, S]),
     "frl_vq_bwd": (c_int, [P, P, P, P, P, P, P, F, L, I, I, P, P, P, I, P, S, P]),
+    "frl_vq_bwd_scalars": (c_int, [P, P, P, P, P, P, P, P, F, L, I, I, P, P, P, I, P, S, P]),
     "frl_vq_ema_update": (c_int, [P, P, I, I, F, F, P, P, P, P, P]),
     "frl_vq_revive_dead_codes": (c_int, [P, P, L, P, L, I, I, ctypes.c_uint64, P, P, P, I, P]),
     "frl_groupnorm_fwd": (c_int, [P, P, P, P, P, P, I, I, I, I, F, I, I, P]),

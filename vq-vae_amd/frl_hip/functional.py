@@ -19,6 +19,13 @@ def _c(t: Optional[torch.Tensor]):
     return None if t is None else (t if t.is_contiguous() else t.contiguous())
 
 
+def _lean() -> bool:
+    """The autograd nodes of the train step issue no framework launch of their own: no zero-filled gradients for outputs nothing
+    differentiates, no copy of the quantizer's statistics, no stacking of its two upstream scalars.  FRL_HIP_DISABLE=launches restores
+    those launches (A/B runs), and so does ops.set_lean(False) (the data-parallel step); the results are the same bit for bit."""
+    return ops.lean_enabled()
+
+
 def _wanted(ctx, first: int, grads):
     """grads[i] is the gradient of forward input first + i: those autograd does not want (a frozen parameter) come back as None, and
     the tensors the kernels computed anyway are handed to ops.discard (inside ops.deferred_reductions their parked reductions still write
@@ -126,11 +133,15 @@ class ScalarCombineFn(Function):
         ctx.mults = mults                                           # device scalars (no gradient: schedule values), read again in the backward
         ctx.promises = promises                                     # per term: the gradient it was promised (one-pass decoder loss) | None
         ctx.mark_non_differentiable(*res[1:])
+        if _lean():
+            ctx.set_materialize_grads(False)                        # (no zero-filled "gradients" of the flag and the reported sub-total)
         return res if aux_coefs is not None else res + (None,)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g, g_ok, g_aux):
+        if g is None:
+            return (None,) * (4 + len(ctx.coefs))
         gg = ops.scalar_fanout(g.reshape(1).float().contiguous(), ctx.coefs, ctx.mults, ctx.promises)
         return (None, None, None, None) + tuple(gg[i] for i in range(len(ctx.coefs)))
 
@@ -405,11 +416,15 @@ class FilmFusedFn(Function):
         z, gamma, beta = ops.film_fused_fwd(z_type, h, params)
         ctx.save_for_backward(h, z_type, *params)
         ctx.mark_non_differentiable(gamma, beta)
+        if _lean():
+            ctx.set_materialize_grads(False)                        # (no zero-filled "gradients" of gamma and beta: two [B,HW,12] fills per step)
         return z, gamma, beta
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, _dg, _db):
+        if dz is None:
+            return (None,) * len(ctx.saved_tensors)
         h, z_type, *params = ctx.saved_tensors
         dh, grads = ops.film_fused_bwd(z_type, h, _c(dz), params)
         return (dh if ctx.needs_input_grad[0] else None, None) + _wanted(ctx, 2, grads)
@@ -444,14 +459,16 @@ class VQFn(Function):
 
     @staticmethod
     def forward(ctx, z, codebook, prep=None):
-        idx, zq, stats, counts = ops.vq_assign(z, codebook, prep)
-        d = z.shape[-1]
-        n = z.numel() // d
+        # stats = {sum ||z - z_q||^2, perplexity, rows re-evaluated, mean squared error}: the two loss terms are numerically equal; the three
+        # differentiable outputs are views of one copy, not of the non-differentiable stats.  The kernel that writes stats stores the copy
+        # as well (no copy launch)
+        if _lean():
+            idx, zq, stats, counts, st = ops.vq_assign(z, codebook, prep, stats_copy=True)
+        else:
+            idx, zq, stats, counts = ops.vq_assign(z, codebook, prep)
+            st = stats.clone()
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(z, codebook, idx, counts, zq)
-        # stats = {sum ||z - z_q||^2, perplexity, rows re-evaluated, mean squared error}: the two loss terms are numerically equal; the three
-        # differentiable outputs are views of one copy (the single launch the two loss terms cost before), not of the non-differentiable stats
-        st = stats.clone()
         ctx.mark_non_differentiable(idx, counts, stats)
         return zq, st[3], st.narrow(0, 3, 1).reshape(()), st[1], idx, counts, stats
 
@@ -459,6 +476,15 @@ class VQFn(Function):
     @once_differentiable
     def backward(ctx, g_zq, g_cb, g_cm, g_perp, g_idx, g_counts, g_stats):
         z, codebook, idx, counts, zq = ctx.saved_tensors
+
+        def scalar_ok(g):
+            return g is None or (g.dtype == torch.float32 and g.numel() == 1 and g.device == z.device)
+
+        if _lean() and scalar_ok(g_cm) and scalar_ok(g_cb):
+            # the kernels read the two upstream scalars where autograd left them (None: no gradient for that term)
+            gz, ge, _ = ops.vq_bwd(_c(g_zq), z, codebook, idx, counts, None, 1.0, want_gz=ctx.needs_input_grad[0],
+                                   want_ge=ctx.needs_input_grad[1], zq=zq, scalars=(g_cm, g_cb))
+            return gz, ge, None
         if g_cm is not None and g_cb is not None:
             gs = torch.stack([g_cm.reshape(()).float(), g_cb.reshape(()).float()])      # one launch
         else:

@@ -176,6 +176,10 @@ class VQVAE(RepresentationModel):
         # registers anyway, where that one-launch chain applies (RepresentationModel.phase_chain_xtype); the result is bit for bit
         # ops.mean_time(tile).  False: the separate mean_time pass (A/B runs).
         self.chain_xtype = True
+        # A VQVAETrainer with the HIP optimizer keeps the quantizers' prepared images current inside the launch that rewrites the weight
+        # images behind the optimizer (ops.PackCache.add_quantizer: no vq_prepare launch per step) and seeds loss.backward() with a cached
+        # unit gradient (no ones_like fill per step).  False: the stand-alone prepare and autograd's own root gradient (A/B runs); same bits.
+        self.lean_step = True
         self._grad_scale_dev = {}
         # The phase path is conditioned on stopgrad(z_type): forward AND backward of the two branches are independent, so the phase
         # branch runs on a side HIP stream next to VQ + type decoder (forward) and next to the whole type-path backward.

@@ -92,6 +92,28 @@ class PackCache:
         if self.handle <= 0:
             check(self.handle, "frl_pack_cache_create")
         self._prev = 0
+        self._quantizers = {}                               # (id(quantizer), image address, dtype) -> (quantizer, dtype, image, codebook)
+
+    def add_quantizer(self, quantizer) -> bool:
+        """The prepared codebook image of `quantizer` (models.vqvae.VectorQuantizer.prepared) becomes a job of refresh(): the launch that
+        rewrites the weight images behind the optimizer writes norms, fragments and control block of the image too, with the arithmetic
+        of `vq_prepare`, and refresh() then marks the image as current for the codebook version it read.  Needs an image to exist (one
+        forward has run); False when there is none yet.  Registering again is free."""
+        prep = quantizer._prepared
+        if prep is None or prep[0][2] is None:
+            return False
+        dtype, buf, cb = prep[0][2], prep[1], quantizer.codebook
+        key = (id(quantizer), buf.data_ptr(), cb.data_ptr(), dtype)
+        if key not in self._quantizers:
+            if cb.dtype != torch.float32 or not cb.is_contiguous() or cb.device != self.arena.device:
+                return False
+            if any(k[1] == key[1] for k in self._quantizers):   # one job per image: a second row dtype keeps the stand-alone prepare
+                return False
+            k, d = cb.shape
+            check(_lib.load().frl_pack_cache_add_vq(self.handle, _p(cb), k, d, BF16 if dtype == torch.bfloat16 else F32, _p(buf), buf.numel()),
+                  "frl_pack_cache_add_vq")
+            self._quantizers[key] = (quantizer, dtype, buf, cb)
+        return True
 
     def __enter__(self):
         self._prev = _lib.load().frl_pack_cache_activate(self.handle)
@@ -103,6 +125,14 @@ class PackCache:
 
     def refresh(self) -> None:
         check(_lib.load().frl_pack_cache_refresh(self.handle, _stream()), "frl_pack_cache_refresh")
+        for qz, dtype, buf, cb in self._quantizers.values():
+            if qz._prepared is None or qz._prepared[1] is not buf:
+                continue                                    # the quantizer moved on to another image: this job writes a buffer nobody reads
+            # the launch read the codebook as it is now: the image is current for this version (any later in-place change bumps the
+            # version and `prepared()` falls back to the stand-alone prepare).  A codebook that changed its storage since the
+            # registration was NOT what the job read: the image is then unknown.
+            same = qz.codebook is cb or qz.codebook.data_ptr() == cb.data_ptr()
+            qz._prepared = ((cb.data_ptr(), qz.codebook._version, dtype) if same else (None, None, dtype), buf)
 
     @property
     def images(self) -> int:
@@ -424,9 +454,11 @@ def vq_prepare(codebook: torch.Tensor, n_rows: int, dtype: torch.dtype, out: Opt
 
 
 @_timed("vq_assign")
-def vq_assign(z: torch.Tensor, codebook: torch.Tensor, prep: Optional[torch.Tensor] = None):
+def vq_assign(z: torch.Tensor, codebook: torch.Tensor, prep: Optional[torch.Tensor] = None, stats_copy: bool = False):
     """z [N,d] rows, codebook [K,d] f32 -> (idx int32 [N], z_q [N,d], stats f32 [4], counts int32 [K]).
-    prep: image from `vq_prepare` for this codebook content and z.dtype (None: built inside the call)."""
+    prep: image from `vq_prepare` for this codebook content and z.dtype (None: built inside the call).
+    stats_copy: a fifth result, a second float32 [4] tensor with the bits of `stats`, stored by the kernel that writes `stats` (what
+    `stats.clone()` gives, without the copy launch)."""
     k, d = codebook.shape
     _chk_rows(z, d, "vq_assign.z")
     cb = _f32(codebook, "codebook")
@@ -439,6 +471,11 @@ def vq_assign(z: torch.Tensor, codebook: torch.Tensor, prep: Optional[torch.Tens
     counts = torch.empty(k, dtype=torch.int32, device=z.device)
     if prep is not None and (prep.dtype != torch.uint8 or prep.device != z.device or prep.numel() < lib.frl_vq_prepared_bytes(k, d)):
         raise ValueError("vq_assign: prep is not a prepared-codebook image for this codebook")
+    if stats_copy:
+        stats2 = torch.empty(4, dtype=torch.float32, device=z.device)
+        check(lib.frl_vq_assign_fwd_stats2(_p(z), _p(cb), _p(prep), n, k, d, _p(idx), _p(zq), _p(stats), _p(stats2), _p(counts), _dt(z), _p(ws),
+                                           ws.numel(), _stream()), "frl_vq_assign_fwd")
+        return idx, zq, stats, counts, stats2
     check(lib.frl_vq_assign_fwd_prepared(_p(z), _p(cb), _p(prep), n, k, d, _p(idx), _p(zq), _p(stats), _p(counts), _dt(z), _p(ws),
                                          ws.numel(), _stream()), "frl_vq_assign_fwd")
     return idx, zq, stats, counts
@@ -447,9 +484,11 @@ def vq_assign(z: torch.Tensor, codebook: torch.Tensor, prep: Optional[torch.Tens
 @_timed("vq_bwd")
 def vq_bwd(g_out: Optional[torch.Tensor], z: torch.Tensor, codebook: torch.Tensor, idx: torch.Tensor,
            counts: torch.Tensor, gscale: Optional[torch.Tensor], beta: float, want_gz: bool = True,
-           want_ge: bool = True, want_sums: bool = False, zq: Optional[torch.Tensor] = None):
+           want_ge: bool = True, want_sums: bool = False, zq: Optional[torch.Tensor] = None, scalars=None):
     """g_z = g_out + gscale[0] beta 2/(N d) (z - e_idx), g_E = gscale[1] 2/(N d) (n_k e_k - S_k), S_k = per-code sums of z.  The kernels
-    read every operand as raw rows of z's dtype / int32 / float32, so anything else is refused here, before the launch."""
+    read every operand as raw rows of z's dtype / int32 / float32, so anything else is refused here, before the launch.
+    scalars = (g_commit, g_codebook) instead of gscale: the two upstream gradients as separate float32 device scalars, read where they
+    lie (no stacking launch); a None entry means that no gradient arrives for that term (the bits a zero scalar gives)."""
     if codebook.dim() != 2:
         raise ValueError(f"vq_bwd: codebook must be [K, d], got {tuple(codebook.shape)}")
     k, d = codebook.shape
@@ -471,6 +510,12 @@ def vq_bwd(g_out: Optional[torch.Tensor], z: torch.Tensor, codebook: torch.Tenso
         raise ValueError("vq_bwd.gscale: expected a contiguous float32 tensor of at least 2 elements on the device of z")
     if codebook.device != z.device:
         raise ValueError("vq_bwd: codebook and z live on different devices")
+    if scalars is not None:
+        if gscale is not None or len(scalars) != 2:
+            raise ValueError("vq_bwd: scalars is a pair (g_commit, g_codebook) and replaces gscale")
+        for s in scalars:
+            if s is not None and (s.dtype != torch.float32 or s.device != z.device or s.numel() != 1):
+                raise ValueError("vq_bwd.scalars: expected float32 scalars on the device of z (or None)")
     lib = _lib.load()
     ws = workspace(lib.frl_vq_workspace_bytes(n, k, d), z.device)
     gz = torch.empty_like(z) if want_gz else None
@@ -478,7 +523,11 @@ def vq_bwd(g_out: Optional[torch.Tensor], z: torch.Tensor, codebook: torch.Tenso
     sums = torch.empty(k, d, dtype=torch.float32, device=z.device) if want_sums else None
     cb32 = _f32(codebook, "codebook")
     if _DEFER["on"]:                                            # the parked codebook-gradient reduction reads these when the flush runs
-        _DEFER["keep"] += [t for t in (counts, gscale, cb32) if t is not None]
+        _DEFER["keep"] += [t for t in (counts, gscale, cb32) + tuple(scalars or ()) if t is not None]
+    if scalars is not None:
+        check(lib.frl_vq_bwd_scalars(_p(g_out), _p(z), _p(zq), _p(cb32), _p(idx), _p(counts), _p(scalars[0]), _p(scalars[1]), float(beta),
+                                     n, k, d, _p(gz), _p(ge), _p(sums), _dt(z), _p(ws), ws.numel(), _stream()), "frl_vq_bwd_scalars")
+        return gz, ge, sums
     check(lib.frl_vq_bwd(_p(g_out), _p(z), _p(zq), _p(cb32), _p(idx), _p(counts), _p(gscale), float(beta),
                          n, k, d, _p(gz), _p(ge), _p(sums), _dt(z), _p(ws), ws.numel(), _stream()), "frl_vq_bwd")
     return gz, ge, sums
@@ -1230,6 +1279,21 @@ def edge_smooth_bwd(d_smoothed, x, a_soft, b_soft, rank: int, coarse_dilation: i
                                                   b, h, w, c, rank, coarse_dilation, _dt(x), _stream()),
           "frl_edge_smooth_stencil_bwd")
     return dx, da, db
+
+
+_LEAN = {"on": True}
+
+
+def set_lean(on: bool) -> bool:
+    """Process-wide (the backward runs on autograd's worker threads): False makes the autograd nodes issue the framework launches they
+    issued before `functional._lean` existed (zero-filled gradients, the statistics clone, the stacked scalars).  A trainer with an active
+    data-parallel reducer switches it off for its steps: that step is left exactly as it was.  Returns the previous setting."""
+    was, _LEAN["on"] = _LEAN["on"], bool(on)
+    return was
+
+
+def lean_enabled() -> bool:
+    return _LEAN["on"] and fusion_enabled("launches")
 
 
 def fusion_enabled(name: str) -> bool:

@@ -303,17 +303,47 @@ class VQVAETrainer:
         """loss.backward(); single-process training parks the slab reductions of the weight-gradient kernels and runs them in one launch
         (ops.deferred_reductions).  Data parallel keeps them where they are: the bucket hooks read each gradient the moment autograd
         delivers it."""
+        seed = self._unit_gradient(loss)
         if self.defer_reductions and self.hip_opt and not (self.reducer is not None and self.reducer.active):
             from .. import ops
             with ops.deferred_reductions(self.opt.params):
-                loss.backward()
+                loss.backward(seed)
         else:
-            loss.backward()
+            loss.backward(seed)
+
+    def _unit_gradient(self, loss):
+        """The root gradient of loss.backward() as a cached device scalar 1.0 (autograd otherwise fills a fresh ones_like per step: one
+        launch); None -- autograd's own -- off the GPU, for another loss shape or with `model.lean_step = False`."""
+        if not (self._lean() and loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32):
+            return None
+        one = self.__dict__.setdefault("_unit_grads", {}).get(loss.device)
+        if one is None:
+            one = self._unit_grads[loss.device] = torch.ones((), dtype=torch.float32, device=loss.device)
+        return one
+
+    def _lean(self) -> bool:
+        """model.lean_step, single process only: the data-parallel step keeps every launch it had (root gradient, stand-alone prepare,
+        and -- through ops.set_lean -- the autograd nodes' own)."""
+        on = bool(getattr(self.model, "lean_step", False)) and not (self.reducer is not None and self.reducer.active)
+        if self.hip_opt:
+            from .. import ops
+            ops.set_lean(not (self.reducer is not None and self.reducer.active))
+        return on
+
+    def _refresh_images_and_codebooks(self) -> None:
+        """Behind the optimizer: ONE launch rewrites the weight images and, for every quantizer whose prepared image exists, that image too
+        (norms, fragments, control block: ops.PackCache.add_quantizer).  Data parallel and `model.lean_step = False` keep the quantizers on the
+        stand-alone prepare, as does everything that changes a codebook behind this launch (EMA commit, revival, load_state_dict)."""
+        if self.pack_cache is not None and self._lean() and hasattr(self.model, "_quantizers"):
+            for qz in self.model._quantizers():
+                self.pack_cache.add_quantizer(qz)
+        self._images_refresh()
 
     def _step_body(self, tile, mask):
         """forward -> device isfinite flag -> backward -> clip + AdamW -> codebook hooks -> fragment-image refresh (no host-side
         schedule, no host sync): the part of `step` that a graph can hold."""
         self.model.train()
+        self._lean()                                           # (before the forward: its autograd nodes read the setting)
         self.opt.zero_grad(set_to_none=True)
         dp = self.reducer is not None and self.reducer.active
         if dp:
@@ -340,7 +370,7 @@ class VQVAETrainer:
             grads = [fg[id(p)] if p.grad is not None else None for p in self.opt.params]
             ok = (self.reducer.flag_result() == 0).float()         # 1 <=> no rank reported a non-finite loss
         out["grad_norm"] = self.opt.step(self.max_norm, grads, ok)
-        self._images_refresh()
+        self._refresh_images_and_codebooks()
         if getattr(self.model, "defer_codebook_hooks", False):
             self.model.commit_codebook_hooks(ok)
         if hasattr(self.model, "_quantizers"):
@@ -432,6 +462,7 @@ class VQVAETrainer:
             pass
         self._set_lambda_vq()
         self.model.train()
+        self._lean()                                           # (before the forward: its autograd nodes read the setting)
         self.opt.zero_grad(set_to_none=True)
         self._images_current()
         if self.pack_cache is not None:
@@ -476,7 +507,7 @@ class VQVAETrainer:
                 if ok is not None:
                     ok = (self.reducer.flag_result() == 0).float()   # 1 <=> no rank reported a non-finite loss
             out["grad_norm"] = self.opt.step(self.max_norm, grads, ok)
-            self._images_refresh()
+            self._refresh_images_and_codebooks()
             if getattr(self.model, "defer_codebook_hooks", False):
                 self.model.commit_codebook_hooks(ok)                   # EMA / usage window: gated by the same device flag
         else:
