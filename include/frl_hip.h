@@ -103,6 +103,12 @@ int frl_conv3x3_bwd_data(const void* dy, const void* y, int act, const float* w,
 int frl_conv3x3_bwd_data_fused(const void* dy, const void* y, int act, const float* w, void* dx, const void* add,
                                const void* sub_from, void* out2, int B, int H, int W, int Cin, int Cout, int dtype, void* ws,
                                size_t ws_bytes, frl_stream_t stream);
+/* frl_conv3x3_bwd_data_fused whose add operand is the gate blend's d_residual, formed in the epilogue instead of read: dx = conv(...) +
+ * round(dout * gate) (rounded to the tensor dtype, as frl_gate_blend_bwd stores it with min_gate <= 0), out2 = dout - dx.  gate, dout and
+ * out2 [B][H][W][Cin] are all required; same bits as the two-step form. */
+int frl_conv3x3_bwd_data_blend(const void* dy, const void* y, int act, const float* w, void* dx, const void* gate, const void* dout,
+                               void* out2, int B, int H, int W, int Cin, int Cout, int dtype, void* ws, size_t ws_bytes,
+                               frl_stream_t stream);
 /* dx = conv^T(dy .* act'(y)) .* out_act'(out_y): out_y [B][H][W][Cin] is the output of the ReLU / sigmoid (out_act) that the NEXT backward
  * step differentiates through at the same pixels; that step's calls then take dx with act = FRL_ACT_NONE (no mask pass over their input:
  * 16-35 us per 3x3 backward-data call and 6-15 us per weight-gradient call at BASELINE configs[1]). */
@@ -169,6 +175,11 @@ int frl_sobel_fwd(const void* x, void* g, int B, int H, int W, int C, int dtype,
 int frl_sobel_bwd(const void* dg, void* dx, int B, int H, int W, int C, int dtype, frl_stream_t stream);
 /* dx = sobel^T(dg) + dx_add (dx_add [B][H][W][C] or null): x also feeds the filter bank, whose dx arrives through dx_add */
 int frl_sobel_bwd_add(const void* dg, void* dx, const void* dx_add, int B, int H, int W, int C, int dtype, frl_stream_t stream);
+/* A/B hook: 1 (default) = bf16 Sobel calls whose image row is one workgroup of 16-byte channel vectors (W * C / 8 == 256: 32 x 64) take the
+ * row-band streaming kernels, 0 = every call takes the gather kernels; same bits either way.  Returns the previous setting. */
+int frl_sobel_stream(int on);
+/* Tuning hook: rows per workgroup of the streaming route (1..64, default 8; other values change nothing).  Returns the previous height. */
+int frl_sobel_stream_band(int rows);
 /* directional bank + rank-R mixing (spatial.py:224-237,300-331): a_logit [P][8R] (k*R+r), b_logit [P][C*R] (c*R+r);
  * outputs smoothed, residual = x - smoothed, and the softmaxed maps a_soft / b_soft saved for the backward. */
 int frl_edge_smooth_stencil_fwd(const void* x, const void* a_logit, const void* b_logit, void* smoothed, void* residual,
@@ -217,6 +228,7 @@ int frl_film_fused_bwd(const void* z_type, const void* h, const void* dz, const 
 /* out = smoothed + max(gate_raw, min_gate) * residual (spatial.py:333-335); n = element count */
 int frl_gate_blend_fwd(const void* smoothed, const void* residual, const void* gate_raw, float min_gate, void* out,
                        void* gate_out, int64_t n, int dtype, frl_stream_t stream);
+/* d_residual may be null (both forms): only d_gate_raw is stored then (frl_conv3x3_bwd_data_blend forms d_residual itself). */
 int frl_gate_blend_bwd(const void* dout, const void* dgate_ext, const void* residual, const void* gate_raw, float min_gate,
                        void* d_residual, void* d_gate_raw, int64_t n, int dtype, frl_stream_t stream);
 /* The same with sigmoid_mask != 0: d_gate_raw is returned multiplied by gate_raw (1 - gate_raw), the derivative of the sigmoid that produced

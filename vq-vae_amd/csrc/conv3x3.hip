@@ -159,8 +159,16 @@ __device__ __forceinline__ void c3_halo_commit(const C3Halo<T, CK, NTHR, TH, MAS
   }
 }
 
+// epi_mode 4: the blend's d_residual = dout * gate, rounded to the tensor dtype as the stand-alone gate_blend_bwd kernel stores it.  The
+// product is its own rounding step in float32 too (the empty asm keeps it from contracting into the add that follows).
+template <typename T> __device__ __forceinline__ float c3_blend_dres(float d, float g) {
+  float p = d * g;
+  if constexpr (sizeof(T) == 4) asm volatile("" : "+v"(p));
+  return to_f32(from_f32<T>(p));
+}
+
 #ifdef C3_STAMPS
-__device__ unsigned long long* c3_dbg;       // diagnostic build only (tools/diag/c3_stamps.hip)
+__device__ unsigned long long* c3_dbg;      // diagnostic build only (tools/diag/c3_stamps.hip)
 #endif
 // TH: tile height (16 or 32 rows of 16 pixels); a wave owns RPW = TH / 8 consecutive rows.  TH = 32 halves the barriers / halo commits per
 // pixel, doubles the MFMA burst a prefetched halo has to hide behind, and (4 rows per wave) reads the pixel fragments of a column shift
@@ -177,6 +185,8 @@ __global__ __launch_bounds__(512) void conv3x3_kernel(const T* __restrict__ X, c
   // Y2 = Yadd + gate * Ysub (Yadd = smoothed, Ysub = residual; gate taken as rounded for its store, as the stand-alone kernel reads it).
   // epi_mode 2 / 3 (backward-data whose consumer is again a backward pass through an activation): Y = conv * act'(Yadd) with Yadd = the
   // OUTPUT of a ReLU (2) / sigmoid (3) at the same pixel -- the next layer's backward calls then need no mask pass over their input.
+  // epi_mode 4 (backward of the gate blend without a gate floor, Yadd = gate, Ysub = dout): Y = conv + round_T(dout * gate) and Y2 = dout - Y,
+  // i.e. mode 0 with its `add` operand formed here instead of stored by gate_blend_bwd and read back.
   typedef typename DT<T>::frag_t frag_t;
   constexpr int FE = DT<T>::FE;
   constexpr int q = NF * FE, CK = 4 * q;
@@ -357,7 +367,7 @@ __global__ __launch_bounds__(512) void conv3x3_kernel(const T* __restrict__ X, c
             float o[DT<T>::VEC];
 #pragma unroll
             for (int e = 0; e < DT<T>::VEC; ++e) o[e] = v[j + e];
-            if (epi_mode >= 2) {
+            if (epi_mode == 2 || epi_mode == 3) {
               float m[DT<T>::VEC];
               Vec<T>::load(Yadd + yo + j, m);
 #pragma unroll
@@ -378,6 +388,12 @@ __global__ __launch_bounds__(512) void conv3x3_kernel(const T* __restrict__ X, c
             if (Yadd != nullptr) {
               float a[DT<T>::VEC];
               Vec<T>::load(Yadd + yo + j, a);
+              if (epi_mode == 4) {                                // Yadd is the gate: the add operand is formed here, rounded as it was stored
+                float d[DT<T>::VEC];
+                Vec<T>::load(Ysub + yo + j, d);
+#pragma unroll
+                for (int e = 0; e < DT<T>::VEC; ++e) a[e] = c3_blend_dres<T>(d[e], a[e]);
+              }
 #pragma unroll
               for (int e = 0; e < DT<T>::VEC; ++e) o[e] += a[e];
             }
@@ -412,7 +428,7 @@ __global__ __launch_bounds__(512) void conv3x3_kernel(const T* __restrict__ X, c
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             if (cb + r >= Cout) continue;
-            if (epi_mode >= 2) {
+            if (epi_mode == 2 || epi_mode == 3) {
               yp[cb + r] = from_f32<T>(v[r] * act_bwd_from_y(to_f32(Yadd[yo + cb + r]), epi_mode == 2 ? FRL_ACT_RELU : FRL_ACT_SIGMOID));
               continue;
             }
@@ -420,6 +436,13 @@ __global__ __launch_bounds__(512) void conv3x3_kernel(const T* __restrict__ X, c
               const T o = from_f32<T>(v[r]);
               yp[cb + r] = o;
               Y2[yo + cb + r] = from_f32<T>(fmaf(to_f32(o), to_f32(Ysub[yo + cb + r]), to_f32(Yadd[yo + cb + r])));
+              continue;
+            }
+            if (epi_mode == 4) {
+              const float d = to_f32(Ysub[yo + cb + r]);
+              const T o = from_f32<T>(v[r] + c3_blend_dres<T>(d, to_f32(Yadd[yo + cb + r])));
+              yp[cb + r] = o;
+              Y2[yo + cb + r] = from_f32<T>(d - to_f32(o));
               continue;
             }
             if (Yadd != nullptr) v[r] += to_f32(Yadd[yo + cb + r]);
@@ -709,6 +732,15 @@ int frl_conv3x3_bwd_data_fused(const void* dy, const void* y, int act, const flo
                                hipStream_t stream) {
   return c3_dispatch(dy, act != FRL_ACT_NONE ? y : nullptr, act, w, 9, (int64_t)Cin * 9, 1, nullptr, dx, B, H, W, Cout, Cin,
                      FRL_ACT_NONE, dtype, ws, ws_bytes, stream, add, sub_from, out2);
+}
+
+// frl_conv3x3_bwd_data_fused with add = round(dout * gate) formed in the epilogue: dx = conv(...) + dout * gate, out2 = dout - dx.
+int frl_conv3x3_bwd_data_blend(const void* dy, const void* y, int act, const float* w, void* dx, const void* gate, const void* dout,
+                               void* out2, int B, int H, int W, int Cin, int Cout, int dtype, void* ws, size_t ws_bytes,
+                               hipStream_t stream) {
+  if (gate == nullptr || dout == nullptr || out2 == nullptr) return frl_fail(-2, "conv3x3_bwd_data_blend: gate, dout and out2 are required");
+  return c3_dispatch(dy, act != FRL_ACT_NONE ? y : nullptr, act, w, 9, (int64_t)Cin * 9, 1, nullptr, dx, B, H, W, Cout, Cin,
+                     FRL_ACT_NONE, dtype, ws, ws_bytes, stream, gate, dout, out2, 4);
 }
 
 // dx = conv^T(dy .* act'(y)) .* out_act'(out_y): the gradient handed on to a backward pass through the activation that produced out_y

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void gate_blend_bwd_kernel(const T* __restrict
       o2[e] = clamped ? 0.f : fmaf(d[e], r[e], x[e]);
       if (sigmoid_mask) o2[e] *= g[e] * (1.f - g[e]);            // graw = sigmoid(.): hand on the gradient w.r.t. the pre-activation
     }
-    Vec<T>::store(dres + i * V, o1);
+    if (dres != nullptr) Vec<T>::store(dres + i * V, o1);          // (null: the consumer forms dout * gate itself, conv3x3 epi_mode 4)
     Vec<T>::store(dgraw + i * V, o2);
   }
 }

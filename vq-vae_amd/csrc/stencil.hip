@@ -119,6 +119,180 @@ __global__ __launch_bounds__(256) void sobel_bwd_kernel(const T* __restrict__ DG
   }
 }
 
+// ------------------------------------------------------------------------------------------------ Sobel, row-band streaming route
+// bf16 images whose row is exactly one workgroup of channel vectors (W * C / 8 == 256; the project's 32 x 64).  A workgroup owns a band of
+// BH consecutive rows of one image; a thread owns (column, 8-channel vector) and walks the band row by row.  Every input row is requested
+// once per workgroup (three coalesced 16-byte loads: x - 1, x, x + 1; the shifted ones hit the lines the wave's centre load brings in) and
+// feeds the three output rows it touches, whose partial fmaf chains live in a three-row register window.  The rows ahead sit in an
+// unrolled register ring of NR slots, so NR rows per workgroup are in flight while the current one is computed.  Only the band's halo
+// rows (one above, one below) are read twice.  The forward walks DOWN and the backward walks UP: in both the rows then arrive in the
+// (ky, kx) row-major order of the gather kernels' chains, so every output element sees exactly their fmaf sequence: centre skipped,
+// taps outside the image skipped (never multiplied by zero), zero-weight terms kept.
+#define SB_FWD_RING 4
+#define SB_BWD_RING 2
+#define SB_WX(ky, kx) ((float)((kx) - 1) * ((ky) == 1 ? 2.f : 1.f) * 0.25f)
+#define SB_WY(ky, kx) ((float)((ky) - 1) * ((kx) == 1 ? 2.f : 1.f) * 0.25f)
+
+// forward taps of kernel row KY on one input row: v[0] = x - 1, v[1] = x, v[2] = x + 1
+template <int KY>
+__device__ __forceinline__ void sb_fwd_taps(float* gx, float* gy, const float (&v)[3][8], bool hasL, bool hasR) {
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) {
+    if (KY == 1 && kx == 1) continue;
+    const bool ok = kx == 0 ? hasL : kx == 2 ? hasR : true;
+    if (ok) {                                                      // (a branch over the tap, as in the gather kernels: no select per element)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { gx[e] = fmaf(SB_WX(KY, kx), v[kx][e], gx[e]); gy[e] = fmaf(SB_WY(KY, kx), v[kx][e], gy[e]); }
+    }
+  }
+}
+
+// backward taps of kernel row KY on one gradient row: tap kx reads the output pixel at x - (kx - 1); a = its d gx, c = its d gy
+template <int KY>
+__device__ __forceinline__ void sb_bwd_taps(float* o, const float (&a)[3][8], const float (&c)[3][8], bool hasL, bool hasR) {
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) {
+    if (KY == 1 && kx == 1) continue;
+    const int s = 2 - kx;                                          // 0 = x - 1, 1 = x, 2 = x + 1
+    const bool ok = s == 0 ? hasL : s == 2 ? hasR : true;
+    if (ok) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf(SB_WX(KY, kx), a[s][e], fmaf(SB_WY(KY, kx), c[s][e], o[e]));
+    }
+  }
+}
+
+__device__ __forceinline__ void sb_cvt(const bf16x8& r, float* o) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (float)r[e];
+}
+
+template <int NR>
+__global__ __launch_bounds__(256, 4) void sobel_fwd_band_kernel(const bf16* __restrict__ X, bf16* __restrict__ G, int H, int W, int C, int BH,
+                                                             int nbands) {
+  constexpr int V = 8;
+  const int tid = (int)threadIdx.x;
+  const unsigned wg = xcd_remap(blockIdx.x, gridDim.x);            // the bands of one image share an XCD: halo rows hit its L2
+  const int b = (int)(wg / (unsigned)nbands), y0 = (int)(wg % (unsigned)nbands) * BH;
+  const int y1 = y0 + BH < H ? y0 + BH : H;                        // output rows [y0, y1)
+  const int rlo = y0 > 0 ? y0 - 1 : 0, rhi = y1 < H ? y1 + 1 : H;  // input rows [rlo, rhi)
+  const int x = tid / (C / V), c0 = tid * V - x * C;
+  const bool hasL = x > 0, hasR = x < W - 1;
+  const int rowE = W * C;
+  const int dl = hasL ? -C : 0, dr = hasR ? C : 0;                 // border: redirected to the pixel itself, the tap is skipped
+  const bf16* xc = X + (int64_t)b * H * rowE + tid * V;
+  bf16* gp = G + (int64_t)b * H * rowE * 2 + x * 2 * C + c0;
+  bf16x8 ring[NR][3];
+  auto fetch = [&](int j, int r) {
+    const bf16* p = xc + r * rowE;
+    ring[j][0] = *reinterpret_cast<const bf16x8*>(p + dl);
+    ring[j][1] = *reinterpret_cast<const bf16x8*>(p);
+    ring[j][2] = *reinterpret_cast<const bf16x8*>(p + dr);
+  };
+  auto put = [&](int y, const float* gx, const float* gy) {
+    Vec<bf16>::store(gp + y * (2 * rowE), gx);
+    Vec<bf16>::store(gp + y * (2 * rowE) + C, gy);
+  };
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+    if (rlo + j < rhi) fetch(j, rlo + j);
+  float gx[3][V], gy[3][V];                                        // partial chains of output rows r - 1, r, r + 1
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int e = 0; e < V; ++e) { gx[k][e] = 0.f; gy[k][e] = 0.f; }
+  for (int base = rlo; base < rhi; base += NR) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int r = base + j;
+      if (r >= rhi) break;
+      float v[3][V];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sb_cvt(ring[j][k], v[k]);
+      if (r + NR < rhi) fetch(j, r + NR);
+      if (r - 1 >= y0) {                                           // kernel row 2 closes output row r - 1
+        sb_fwd_taps<2>(gx[0], gy[0], v, hasL, hasR);
+        put(r - 1, gx[0], gy[0]);
+      }
+      if (r >= y0 && r < y1) {                                     // (row 0 of the image has no row above: its chain starts here, from the zeros)
+        sb_fwd_taps<1>(gx[1], gy[1], v, hasL, hasR);
+        if (r == H - 1) put(r, gx[1], gy[1]);
+      }
+      if (r + 1 < y1) sb_fwd_taps<0>(gx[2], gy[2], v, hasL, hasR);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        gx[0][e] = gx[1][e]; gy[0][e] = gy[1][e];
+        gx[1][e] = gx[2][e]; gy[1][e] = gy[2][e];
+        gx[2][e] = 0.f; gy[2][e] = 0.f;
+      }
+    }
+  }
+}
+
+template <int NR>
+__global__ __launch_bounds__(256) void sobel_bwd_band_kernel(const bf16* __restrict__ DG, bf16* __restrict__ DX, const bf16* __restrict__ DXADD,
+                                                             int H, int W, int C, int BH, int nbands) {
+  constexpr int V = 8;
+  const int tid = (int)threadIdx.x;
+  const unsigned wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int b = (int)(wg / (unsigned)nbands), y0 = (int)(wg % (unsigned)nbands) * BH;
+  const int y1 = y0 + BH < H ? y0 + BH : H;                        // dx rows [y0, y1)
+  const int rlo = y0 > 0 ? y0 - 1 : 0, rhi = y1 < H ? y1 + 1 : H;  // gradient rows [rlo, rhi), walked from rhi - 1 up to rlo
+  const int x = tid / (C / V), c0 = tid * V - x * C;
+  const bool hasL = x > 0, hasR = x < W - 1;
+  const int rowE = W * C;
+  const int dl = hasL ? -2 * C : 0, dr = hasR ? 2 * C : 0;
+  const bool has_add = DXADD != nullptr;
+  const bf16* gc = DG + (int64_t)b * H * rowE * 2 + x * 2 * C + c0;
+  const bf16* ap = DXADD + (int64_t)b * H * rowE + tid * V;          // (only dereferenced with has_add)
+  bf16* dxp = DX + (int64_t)b * H * rowE + tid * V;
+  bf16x8 ring[NR][6], radd[NR];                                    // a / c at x - 1, x, x + 1; dx_add of the output row whose chain this row opens
+  auto fetch = [&](int j, int r) {
+    const bf16* p = gc + r * (2 * rowE);
+    ring[j][0] = *reinterpret_cast<const bf16x8*>(p + dl);
+    ring[j][1] = *reinterpret_cast<const bf16x8*>(p);
+    ring[j][2] = *reinterpret_cast<const bf16x8*>(p + dr);
+    ring[j][3] = *reinterpret_cast<const bf16x8*>(p + dl + C);
+    ring[j][4] = *reinterpret_cast<const bf16x8*>(p + C);
+    ring[j][5] = *reinterpret_cast<const bf16x8*>(p + dr + C);
+    if (has_add && r - 1 >= y0) radd[j] = *reinterpret_cast<const bf16x8*>(ap + (r - 1) * rowE);
+  };
+  float o[3][V];                                                   // partial chains of dx rows r + 1, r, r - 1
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int e = 0; e < V; ++e) o[k][e] = 0.f;
+  if (has_add && y1 == H) Vec<bf16>::load(ap + (H - 1) * rowE, o[1]);   // the image's last row has no row below: its chain opens with the band
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+    if (rhi - 1 - j >= rlo) fetch(j, rhi - 1 - j);
+  for (int base = rhi - 1; base >= rlo; base -= NR) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int r = base - j;
+      if (r < rlo) break;
+      float a[3][V], c[3][V];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { sb_cvt(ring[j][k], a[k]); sb_cvt(ring[j][3 + k], c[k]); }
+      if (r - 1 >= y0) {                                           // kernel row 0 opens dx row r - 1 from dx_add (or the zeros)
+        if (has_add) sb_cvt(radd[j], o[2]);
+        sb_bwd_taps<0>(o[2], a, c, hasL, hasR);
+      }
+      if (r - NR >= rlo) fetch(j, r - NR);
+      if (r >= y0 && r < y1) {
+        sb_bwd_taps<1>(o[1], a, c, hasL, hasR);
+        if (r == 0) Vec<bf16>::store(dxp, o[1]);
+      }
+      if (r + 1 < y1) {                                            // kernel row 2 closes dx row r + 1
+        sb_bwd_taps<2>(o[0], a, c, hasL, hasR);
+        Vec<bf16>::store(dxp + (r + 1) * rowE, o[0]);
+      }
+#pragma unroll
+      for (int e = 0; e < V; ++e) { o[0][e] = o[1][e]; o[1][e] = o[2][e]; o[2][e] = 0.f; }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ smoothing
 // One workgroup = 256 / TPP pixels; thread (pixel, channel vector).  TPP = power of two >= C / V.
 template <typename T, int V, int R>
@@ -643,10 +817,31 @@ static int smooth_dispatch(bool fwd, const void* a0, const void* a1, const void*
   return frl_fail(-2, "edge_smooth: rank must be 1, 2 or 4");
 }
 
+static int g_sobel_stream = 1;   // A/B hook (frl_sobel_stream): 0 = every call takes the gather kernels
+static int g_sobel_band = 8;     // rows per workgroup of the streaming route (frl_sobel_stream_band)
+
+// the row-band route: bf16, one image row == one workgroup of 16-byte channel vectors, 32-bit offsets inside an image
+static bool sobel_stream_ok(int B, int H, int W, int C, int dtype) {
+  if (!g_sobel_stream || dtype != FRL_BF16 || B <= 0 || H <= 0 || W <= 0 || C % 8 != 0 || (int64_t)W * (C / 8) != 256) return false;
+  const int64_t nb = (H + g_sobel_band - 1) / g_sobel_band;
+  return (int64_t)H * W * C * 2 < ((int64_t)1 << 31) && (int64_t)B * nb < ((int64_t)1 << 31);
+}
+
 extern "C" {
+
+// A/B hook: 1 (default) = bf16 Sobel calls with W * C / 8 == 256 take the row-band streaming kernels, 0 = every call takes the gather
+// kernels; same bits either way.  Returns the previous setting.
+int frl_sobel_stream(int on) { const int was = g_sobel_stream; g_sobel_stream = on ? 1 : 0; return was; }
+// Tuning hook: rows per workgroup of the streaming route (1..64; other values leave it alone).  Returns the previous height.
+int frl_sobel_stream_band(int rows) { const int was = g_sobel_band; if (rows >= 1 && rows <= 64) g_sobel_band = rows; return was; }
 
 // x [B][H][W][C] -> g [B][H][W][2C] = cat[sobel_x(x), sobel_y(x)]
 int frl_sobel_fwd(const void* x, void* g, int B, int H, int W, int C, int dtype, hipStream_t stream) {
+  if (sobel_stream_ok(B, H, W, C, dtype)) {
+    const int nb = (H + g_sobel_band - 1) / g_sobel_band;
+    FRL_LAUNCH((sobel_fwd_band_kernel<SB_FWD_RING>), dim3((unsigned)(B * nb)), dim3(256), 0, stream, (const bf16*)x, (bf16*)g, H, W, C, g_sobel_band, nb);
+    return frl_check_launch("sobel_fwd");
+  }
   if (dtype == FRL_F32 && C % 4 == 0)
     FRL_LAUNCH((sobel_fwd_kernel<float, 4>), dim3(st_grid((int64_t)B * H * W * (C / 4))), dim3(256), 0, stream, (const float*)x, (float*)g, B, H, W, C);
   else if (dtype == FRL_BF16 && C % 8 == 0)
@@ -656,6 +851,12 @@ int frl_sobel_fwd(const void* x, void* g, int B, int H, int W, int C, int dtype,
 }
 
 static int sobel_bwd_launch(const void* dg, void* dx, const void* dx_add, int B, int H, int W, int C, int dtype, hipStream_t stream) {
+  if (sobel_stream_ok(B, H, W, C, dtype)) {
+    const int nb = (H + g_sobel_band - 1) / g_sobel_band;
+    FRL_LAUNCH((sobel_bwd_band_kernel<SB_BWD_RING>), dim3((unsigned)(B * nb)), dim3(256), 0, stream, (const bf16*)dg, (bf16*)dx, (const bf16*)dx_add, H, W, C,
+               g_sobel_band, nb);
+    return frl_check_launch("sobel_bwd");
+  }
   if (dtype == FRL_F32 && C % 4 == 0)
     FRL_LAUNCH((sobel_bwd_kernel<float, 4>), dim3(st_grid((int64_t)B * H * W * (C / 4))), dim3(256), 0, stream, (const float*)dg, (float*)dx,
                (const float*)dx_add, B, H, W, C);

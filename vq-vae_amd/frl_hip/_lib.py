@@ -141,11 +141,14 @@ SIGNATURES = {
     "frl_conv3x3_fwd_gate_blend": (c_int, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, S, P]),
     "frl_conv3x3_bwd_data": (c_int, [P, P, I, P, P, I, I, I, I, I, I, P, S, P]),
     "frl_conv3x3_bwd_data_fused": (c_int, [P, P, I, P, P, P, P, P, I, I, I, I, I, I, P, S, P]),
+    "frl_conv3x3_bwd_data_blend": (c_int, [P, P, I, P, P, P, P, P, I, I, I, I, I, I, P, S, P]),
     "frl_conv3x3_bwd_weight_workspace_bytes": (S, [I, I, I, I, I]),
     "frl_conv3x3_bwd_weight": (c_int, [P, P, I, P, P, P, I, I, I, I, I, I, P, S, I, P]),
     "frl_sobel_fwd": (c_int, [P, P, I, I, I, I, I, P]),
     "frl_sobel_bwd": (c_int, [P, P, I, I, I, I, I, P]),
     "frl_sobel_bwd_add": (c_int, [P, P, P, I, I, I, I, I, P]),
+    "frl_sobel_stream": (c_int, [I]),
+    "frl_sobel_stream_band": (c_int, [I]),
     "frl_edge_smooth_stencil_fwd": (c_int, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "frl_edge_smooth_stencil_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "frl_smooth_heads_supported": (c_int, [I, I, I, I]),

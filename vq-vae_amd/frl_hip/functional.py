@@ -273,7 +273,9 @@ class SpatialSmoothFn(Function):
         # sigmoid' of the gate; epilogue of the gate net's second backward-data: relu' of g1; mixing-heads backward: relu' of feat), so the six
         # 3x3 backward calls run without a mask pass over their input (16-35 us per backward-data, 6-15 us per weight gradient)
         pre = ops.fusion_enabled("premask")
-        dres, dgraw = ops.gate_blend_bwd(dout, _c(dgate), res, gate_raw, min_gate, sigmoid_mask=pre)
+        # without a gate floor the blend's d(residual) = dout * gate is formed in the epilogue of the backward-data call that consumes it
+        fold = min_gate <= 0.0 and ops.fusion_enabled("dres")
+        dres, dgraw = ops.gate_blend_bwd(dout, _c(dgate), res, gate_raw, min_gate, sigmoid_mask=pre, want_dres=not fold)
         a2, y2 = (ACT_NONE, None) if pre else (ACT_SIGMOID, gate_raw)
         if pre:
             dg1 = ops.conv3x3_bwd_data(dgraw, w_g2, None, ACT_NONE, out_y=g1, out_act=ACT_RELU)
@@ -293,7 +295,10 @@ class SpatialSmoothFn(Function):
         dw_g2, db_g2 = wgrad3(4, dgraw, g1, y2, a2)
         a0, y0 = (ACT_NONE, None) if pre else (ACT_RELU, g1)
         # residual: blend term + gate-net term in one store; d(smoothed) - d(residual) (residual = x - smoothed) as the second output
-        dres_tot, d_tot = ops.conv3x3_bwd_data(dg1, w_g0, y0, a0, add=dres, sub_from=dout)
+        if fold:
+            dres_tot, d_tot = ops.conv3x3_bwd_data(dg1, w_g0, y0, a0, gate=gate_raw, sub_from=dout)
+        else:
+            dres_tot, d_tot = ops.conv3x3_bwd_data(dg1, w_g0, y0, a0, add=dres, sub_from=dout)
         dw_g0, db_g0 = wgrad3(3, dg1, res, y0, a0)
         pre_f = pre and ctx.fused_heads
         if ctx.fused_heads:

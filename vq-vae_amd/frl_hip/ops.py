@@ -799,9 +799,10 @@ def gate_blend_fwd(smoothed, residual, gate_raw, min_gate: float):
 
 
 @_timed("gate_blend_bwd")
-def gate_blend_bwd(dout, dgate_ext, residual, gate_raw, min_gate: float, sigmoid_mask: bool = False):
-    """-> (d residual, d gate_raw); sigmoid_mask: d gate_raw comes back multiplied by gate_raw (1 - gate_raw) (gradient w.r.t. the pre-activation)."""
-    dres = torch.empty_like(dout)
+def gate_blend_bwd(dout, dgate_ext, residual, gate_raw, min_gate: float, sigmoid_mask: bool = False, want_dres: bool = True):
+    """-> (d residual, d gate_raw); sigmoid_mask: d gate_raw comes back multiplied by gate_raw (1 - gate_raw) (gradient w.r.t. the pre-activation).
+    want_dres=False: d residual is neither stored nor returned (None): conv3x3_bwd_data(gate=...) forms it in its epilogue."""
+    dres = torch.empty_like(dout) if want_dres else None
     dgraw = torch.empty_like(dout)
     check(_lib.load().frl_gate_blend_bwd_masked(_p(dout), _p(dgate_ext), _p(residual), _p(gate_raw), float(min_gate), _p(dres),
                                                 _p(dgraw), dout.numel(), _dt(dout), int(sigmoid_mask), _stream()), "frl_gate_blend_bwd_masked")
@@ -1190,14 +1191,24 @@ def conv3x3_fwd_gate_blend(x, w, bias, smoothed, residual):
 
 
 @_timed("conv3x3_bwd_data")
-def conv3x3_bwd_data(dy, w, y=None, act: int = ACT_NONE, add=None, sub_from=None, out_y=None, out_act: int = ACT_NONE):
+def conv3x3_bwd_data(dy, w, y=None, act: int = ACT_NONE, add=None, sub_from=None, out_y=None, out_act: int = ACT_NONE, gate=None):
     """dx = conv3x3^T(dy .* act'(y)) (+ add).  With sub_from the call returns (dx, sub_from - dx): both extras ride in the epilogue.
-    out_y / out_act (instead of add / sub_from): dx .* out_act'(out_y) -- the gradient arrives at the next backward step already masked."""
+    out_y / out_act (instead of add / sub_from): dx .* out_act'(out_y) -- the gradient arrives at the next backward step already masked.
+    gate (with sub_from, instead of add): add = sub_from * gate rounded to the tensor dtype, formed in the epilogue (the gate blend's d residual)."""
     b, h, wd, cout = dy.shape
     cin = w.shape[1]
     dx = torch.empty(b, h, wd, cin, dtype=dy.dtype, device=dy.device)
     lib = _lib.load()
     ws = workspace(lib.frl_conv_workspace_bytes(cin, cout, 9), dy.device)
+    if gate is not None:
+        if add is not None or out_y is not None or sub_from is None:
+            raise ValueError("conv3x3_bwd_data: gate needs sub_from and combines with neither add nor out_y")
+        _chk_like(gate, dx, "conv3x3_bwd_data.gate")
+        _chk_like(sub_from, dx, "conv3x3_bwd_data.sub_from")
+        out2 = torch.empty_like(dx)
+        check(lib.frl_conv3x3_bwd_data_blend(_p(dy), _p(y), act, _p(_f32(w, "w")), _p(dx), _p(gate), _p(sub_from), _p(out2), b, h, wd,
+                                             cin, cout, _dt(dy), _p(ws), ws.numel(), _stream()), "frl_conv3x3_bwd_data_blend")
+        return dx, out2
     if out_y is not None:
         if add is not None or sub_from is not None:
             raise ValueError("conv3x3_bwd_data: out_y does not combine with add / sub_from")
@@ -1236,6 +1247,17 @@ def conv3x3_bwd_weight(dy, x, y=None, act: int = ACT_NONE, scalar_frags: bool = 
 # ----------------------------------------------------------------------------------------------
 # fixed stencils of EdgeAwareSmoothingConv2D (csrc/stencil.hip)
 # ----------------------------------------------------------------------------------------------
+def sobel_stream(on: bool) -> bool:
+    """A/B hook (include/frl_hip.h: frl_sobel_stream): True (default) = bf16 Sobel calls with W * C / 8 == 256 take the row-band streaming
+    kernels, False = every call takes the gather kernels; same bits.  Returns the previous setting."""
+    return bool(_lib.load().frl_sobel_stream(1 if on else 0))
+
+
+def sobel_stream_band(rows: int = 0) -> int:
+    """Rows per workgroup of the streaming Sobel route (1..64); returns the previous height, rows=0 only reads it."""
+    return int(_lib.load().frl_sobel_stream_band(int(rows)))
+
+
 @_timed("sobel_fwd")
 def sobel_fwd(x):
     b, h, w, c = x.shape
