@@ -812,6 +812,27 @@ int frl_probe_evaluate(const float* A, int Ta, int Da, const float* Bs, int Tb, 
                        int B, int T, int64_t P, const float* pivot, const float* Wc, const float* bc, int workgroups, double* E, int64_t* n,
                        float* pred, void* ws, size_t ws_bytes, frl_stream_t stream);
 
+/* ---- the phase probe's "full" design (csrc/probe_full.hip) --------------------------------------------------------------------------
+ * [z_type | z_phase | z_type (x) z_phase] of fit_phase_linear_probe.py.  The inputs are those of the frl_probe_* calls with A = z_type
+ * (Da = Dt) and Bs = z_phase (Db = Dp), both required.  Limits (else -2): 1 <= Dt <= 64, 1 <= Dp <= 16, Dq = Dt Dp <= 768,
+ * 1 <= Cy <= 16, Ta, Tb, Ty each 1 or T, B T P < 2^31, workgroups 0 (the library's choice) or 1..4096.  C = Dt + Dp + Cy.
+ * frl_probe_full_accumulate: with x' = x - pivot_x, p' = p - pivot_p, y' = y - pivot_y (float32 subtractions of the frl_probe_pivot of
+ * the fit; zero rows where the mask is), c = [x' | p' | y' | m] and q' = x' (x) p' (column i Dp + a = x'_i p'_a, one float32 product),
+ * Scq [C+1][Dq] += c^T q' and Sqq [Dq][Dq] += q'^T q' (double, both triangles).  c^T c and the count are frl_probe_accumulate's, called
+ * with the same inputs and pivot.  Exact float32 fmaf chains inside a workgroup, the workgroups' slabs added in double in a fixed
+ * order; all-zero mask tiles are not read.  Scq and Sqq are zeroed by the caller before the first call.
+ * frl_probe_full_evaluate: pred_c = beta_c + x' . u_c + p' . v_c + x'^T Omega_c p' with beta [Cy], u [Cy][Dt], v [Cy][Dp],
+ * omega [Cy][Dt][Dp], as a float32 fmaf chain: h_a = sum_i x'_i Omega_c[i][a] in i order from 0, then from beta_c the x'_i u_c[i] in i
+ * order, the p'_a v_c[a] in a order, the h_a p'_a in a order.  E, n and pred are those of frl_probe_evaluate.
+ * No float atomics: every result is bit-identical from run to run.  Workspace (16-byte aligned): frl_probe_full_workspace_bytes. */
+size_t frl_probe_full_workspace_bytes(int Dt, int Dp, int Cy, int workgroups);
+int frl_probe_full_accumulate(const float* A, int Ta, int Dt, const float* Bs, int Tb, int Dp, const float* Y, int Ty, int Cy,
+                              const unsigned char* mask, int B, int T, int64_t P, const float* pivot, int workgroups, double* Scq, double* Sqq,
+                              void* ws, size_t ws_bytes, frl_stream_t stream);
+int frl_probe_full_evaluate(const float* A, int Ta, int Dt, const float* Bs, int Tb, int Dp, const float* Y, int Ty, int Cy,
+                            const unsigned char* mask, int B, int T, int64_t P, const float* pivot, const float* beta, const float* u, const float* v,
+                            const float* omega, int workgroups, double* E, int64_t* n, float* pred, void* ws, size_t ws_bytes, frl_stream_t stream);
+
 /* ---- EVT-stratified diagnostics (csrc/strata.hip) ----------------------------------------------------------------------------------
  * The grouped accumulation of frl/training/compare_gmm_evt.py, phase_evt_diagnostics.py and ysfc_evt_histograms.py.
  * An observation is (b, t, p) with b < B, t < T, p < P (B T P < 2^31).  Its key is codes [B][P], int32 (codes_float = 0) or float32

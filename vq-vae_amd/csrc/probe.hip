@@ -13,25 +13,12 @@
 // fixed order).  frl_probe_evaluate stages the tile with the next one's loads already in registers, gives lane = pixel and
 // wave = targets w, w + 4, .., and runs pred = bc + (x - p) Wc as a float32 fmaf chain in d order with SSE, sum (y - q) and
 // sum (y - q)^2 in double per lane.
-#include "frl_common.hpp"
-#include "frl_host.hpp"
-#include "frl_moments.hpp"
+#include "probe_common.hpp"
 
-#define PROBE_MAX_D 128
-#define PROBE_MAX_CY 16
 #define PROBE_PIVOT_WG 1024
 #define PROBE_EVAL_WG 1024
 
 namespace {
-
-struct ProbeIn {
-  const float* A;
-  const float* Bs;
-  const float* Y;
-  const unsigned char* mask;
-  const float* pivot;
-  int Ta, Da, Tb, Db, Ty, Cy, B, T, P, PT, ntiles, fast;
-};
 
 struct ProbeDims {
   int D, C, C1, CB, ys, nblk, slabF;
@@ -57,8 +44,6 @@ int probe_acc_grid(int64_t ntiles, const ProbeDims& g, int workgroups) {
   return (int)(ntiles < cap ? ntiles : cap);
 }
 
-size_t probe_align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 // block b of the upper triangle, rows first: (0,0) (0,1) .. (0,CB-1) (1,1) ..
@@ -69,45 +54,6 @@ __device__ __forceinline__ void probe_block(int b, int CB, int& ib, int& jb) {
     ++ib;
   }
   jb = ib + b;
-}
-
-// the mask bits of a tile, one per pixel, the same in every wave
-__device__ __forceinline__ unsigned long long probe_mask_bits(const ProbeIn& q, int b, int p0, int lane) {
-  const unsigned char m = lane < moment_tile_rows(q.P, p0) ? q.mask[(size_t)b * q.P + p0 + lane] : (unsigned char)0;
-  return __ballot(m != 0);
-}
-
-// stages columns [col0, col0 + Dn) of a tile straight from memory: src row minus pivot where the bit of `rows` is set, zero elsewhere.
-// vec: the rows are whole 16-byte aligned float4 and so is the LDS row stride
-__device__ __forceinline__ void probe_stage(float* vt, int ys, const float* piv, const float* __restrict__ src, int Ts, int Dn, int col0, bool vec,
-                                            bool centre, const ProbeIn& q, int b, int t, int p0, unsigned long long rows, int tid) {
-  const float* base = src + ((size_t)((int64_t)b * Ts + (Ts > 1 ? t : 0)) * q.P + p0) * Dn;
-  if (vec) {
-    const int q4 = Dn >> 2, n4 = MOMENT_ROWS * q4;
-    for (int e = tid; e < n4; e += 256) {
-      const int row = e / q4, c = (e - row * q4) * 4;
-      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-      if ((rows >> row) & 1ull) {
-        v = *reinterpret_cast<const f32x4*>(base + (size_t)row * Dn + c);
-        if (centre) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] -= piv[col0 + c + j];
-        }
-      }
-      *reinterpret_cast<f32x4*>(vt + row * ys + col0 + c) = v;
-    }
-    return;
-  }
-  const int n = MOMENT_ROWS * Dn;
-  for (int e = tid; e < n; e += 256) {
-    const int row = e / Dn, c = e - row * Dn;
-    float v = 0.f;
-    if ((rows >> row) & 1ull) {
-      v = base[(size_t)row * Dn + c];
-      if (centre) v -= piv[col0 + c];
-    }
-    vt[row * ys + col0 + c] = v;
-  }
 }
 
 // A tile on its way from memory to LDS in the pivot and evaluate kernels.  Where every feature source is rows of whole, 16-byte
@@ -483,32 +429,16 @@ __global__ __launch_bounds__(1024) void probe_eval_reduce_kernel(const double* _
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-int probe_check(const char* what, const float* A, int Ta, int Da, const float* Bs, int Tb, int Db, const float* Y, int Ty, int Cy,
-                const unsigned char* mask, int B, int T, int64_t P, ProbeIn& q) {
-  const char* why = nullptr;
-  if (!A || !Y || !mask) why = "non-null A, Y and mask";
-  else if (Da < 1 || Db < 0 || (Db > 0) != (Bs != nullptr)) why = "Da >= 1, and Bs exactly when Db > 0";
-  else if (Da + Db > PROBE_MAX_D) why = "Da + Db <= 128 feature columns";
-  else if (Cy < 1 || Cy > PROBE_MAX_CY) why = "1 <= Cy <= 16 targets";
-  else if (B < 1 || T < 1 || P < 1) why = "B, T, P >= 1";
-  else if ((Ta != 1 && Ta != T) || (Db > 0 && Tb != 1 && Tb != T) || (Ty != 1 && Ty != T)) why = "Ta, Tb and Ty each 1 or T";
-  else if (!frl_obs_fit(B, T, P)) why = "B * T * P < 2^31 observations";
-  if (why) return frl_failf(-2, "%s: needs %s", what, why);
-  q.A = A; q.Bs = Bs; q.Y = Y; q.mask = mask; q.pivot = nullptr;
-  q.Ta = Ta; q.Da = Da; q.Tb = Db ? Tb : 1; q.Db = Db; q.Ty = Ty; q.Cy = Cy;
-  q.B = B; q.T = T; q.P = (int)P;
-  q.ntiles = frl_moment_tiles(B, T, P, q.PT);
-  // rows of whole float4 on 16-byte boundaries in every feature source: the register-prefetch path
-  q.fast = (Da & 3) == 0 && ((uintptr_t)A & 15) == 0 && (Db == 0 || ((Db & 3) == 0 && ((uintptr_t)Bs & 15) == 0));
-  return 0;
-}
-
 int probe_eval_grid(int64_t ntiles, int workgroups) {
   if (workgroups > 0) return workgroups;
   return (int)(ntiles < PROBE_EVAL_WG ? ntiles : PROBE_EVAL_WG);
 }
 
 }  // namespace
+
+void probe_launch_eval_reduce(const double* dsl, const long long* cnts, int G, int Cy, double* E, long long* n, hipStream_t stream) {
+  FRL_LAUNCH(probe_eval_reduce_kernel, dim3(1), dim3(1024), 0, stream, dsl, cnts, G, Cy, E, n);
+}
 
 extern "C" {
 
@@ -579,7 +509,7 @@ int frl_probe_evaluate(const float* A, int Ta, int Da, const float* Bs, int Tb, 
   double* dsl = (double*)((char*)ws + probe_align16(8 * (size_t)G));
   const size_t lds = sizeof(float) * ((size_t)16 * (Da + Db) + (size_t)MOMENT_ROWS * ys + C);
   FRL_LAUNCH(probe_eval_kernel, dim3((unsigned)G), dim3(256), lds, stream, q, ys, Wc, bc, dsl, cnts, pred);
-  FRL_LAUNCH(probe_eval_reduce_kernel, dim3(1), dim3(1024), 0, stream, (const double*)dsl, (const long long*)cnts, G, Cy, E, (long long*)n);
+  probe_launch_eval_reduce(dsl, cnts, G, Cy, E, (long long*)n, stream);
   return frl_check_launch("probe_evaluate");
 }
 

@@ -129,6 +129,9 @@ SIGNATURES = {
     "frl_probe_pivot": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, P, S, P]),
     "frl_probe_accumulate": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, I, P, P, P, S, P]),
     "frl_probe_evaluate": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, P, P, I, P, P, P, P, S, P]),
+    "frl_probe_full_workspace_bytes": (S, [I, I, I, I]),
+    "frl_probe_full_accumulate": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, I, P, P, P, S, P]),
+    "frl_probe_full_evaluate": (c_int, [P, I, I, P, I, I, P, I, I, P, I, I, L, P, P, P, P, P, I, P, P, P, P, S, P]),
     "frl_strata_workspace_bytes": (S, [I, I, I, I]),
     "frl_strata_contingency": (c_int, [P, I, P, I, P, I, P, I, I, I, L, I, I, P, P, P, P]),
     "frl_strata_moments": (c_int, [P, P, I, P, I, P, I, I, I, I, I, L, I, P, I, I, P, P, P, P, P, P, S, P]),

@@ -2543,6 +2543,71 @@ def probe_evaluate(a: torch.Tensor, bs: Optional[torch.Tensor], y: torch.Tensor,
     return pred
 
 
+# the "full" design [z_type | z_phase | z_type (x) z_phase] (csrc/probe_full.hip)
+PROBE_FULL_MAX_DT, PROBE_FULL_MAX_DP, PROBE_FULL_MAX_DQ = 64, 16, 768
+
+
+def chk_probe_full_dims(dt: int, dp: int, cy: int, workgroups: int = 0, name: str = "probe_full"):
+    """The size limits of the frl_probe_full_* calls that need no data (ValueError)."""
+    if not 1 <= int(dt) <= PROBE_FULL_MAX_DT:
+        raise ValueError(f"{name}: supports 1 <= Dt <= {PROBE_FULL_MAX_DT} z_type columns, got {dt}")
+    if not 1 <= int(dp) <= PROBE_FULL_MAX_DP:
+        raise ValueError(f"{name}: supports 1 <= Dp <= {PROBE_FULL_MAX_DP} z_phase columns, got {dp}")
+    if int(dt) * int(dp) > PROBE_FULL_MAX_DQ:
+        raise ValueError(f"{name}: supports Dt * Dp <= {PROBE_FULL_MAX_DQ} interaction columns, got {int(dt) * int(dp)}")
+    chk_probe_dims(int(dt) + int(dp), cy, workgroups, name)
+
+
+def chk_probe_full(a: torch.Tensor, bs: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, workgroups: int = 0, name: str = "probe_full"):
+    """Every limit of the frl_probe_full_* calls that needs no device (ValueError) -> (B, T, P, Dt, Dp, Cy)."""
+    if bs is None:
+        raise ValueError(f"{name}: needs both sources, z_type and z_phase")
+    if all(isinstance(s, torch.Tensor) and s.dim() == 4 for s in (a, bs, y)):    # the widths first: chk_probe ends on the device check
+        chk_probe_full_dims(a.shape[3], bs.shape[3], y.shape[3], workgroups, name)
+    return chk_probe(a, bs, y, mask, workgroups, name)
+
+
+def probe_full_workspace(dt: int, dp: int, cy: int, device, workgroups: int = 0) -> torch.Tensor:
+    """A workspace for the frl_probe_full_* calls of one probe; it serves the frl_probe_* calls of the same widths too."""
+    chk_probe_full_dims(dt, dp, cy, workgroups, "probe_full_workspace")
+    return _owned_workspace("probe_full_workspace", lambda lib: max(lib.frl_probe_full_workspace_bytes(int(dt), int(dp), int(cy), int(workgroups)),
+                                                                    lib.frl_probe_workspace_bytes(int(dt) + int(dp), int(cy), int(workgroups))), device)
+
+
+@_timed("probe_full_accumulate")
+def probe_full_accumulate(a: torch.Tensor, bs: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, pivot: torch.Tensor, scq: torch.Tensor,
+                          sqq: torch.Tensor, ws: torch.Tensor, workgroups: int = 0) -> None:
+    """Scq f64 [C+1, Dq] += c^T q', Sqq f64 [Dq, Dq] += q'^T q' (include/frl_hip.h: frl_probe_full_accumulate).  No host read."""
+    dims = chk_probe_full(a, bs, y, mask, workgroups, "probe_full_accumulate")
+    c, dq = dims[3] + dims[4] + dims[5], dims[3] * dims[4]
+    _chk_tensor_on("probe_full_accumulate", "pivot", pivot, (c,), torch.float32, a.device)
+    _chk_tensor_on("probe_full_accumulate", "Scq", scq, (c + 1, dq), torch.float64, a.device)
+    _chk_tensor_on("probe_full_accumulate", "Sqq", sqq, (dq, dq), torch.float64, a.device)
+    check(_lib.load().frl_probe_full_accumulate(*_probe_args(a, bs, y, mask, dims), _p(pivot), int(workgroups), _p(scq), _p(sqq), _p(ws), ws.numel(),
+                                                _stream()), "frl_probe_full_accumulate")
+
+
+@_timed("probe_full_evaluate")
+def probe_full_evaluate(a: torch.Tensor, bs: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, pivot: torch.Tensor, beta: torch.Tensor,
+                        u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, e: torch.Tensor, n: torch.Tensor, ws: torch.Tensor,
+                        want_pred: bool = False, workgroups: int = 0):
+    """E f64 [Cy, 3] += (SSE, sum (y - q), sum (y - q)^2), n int64 [1] += the unmasked count for pred = beta + x' u + p' v + x'^T Omega p';
+    -> pred f32 [B, T, P, Cy] | None (include/frl_hip.h: frl_probe_full_evaluate).  No host read."""
+    dims = chk_probe_full(a, bs, y, mask, workgroups, "probe_full_evaluate")
+    b, t, p, dt, dp, cy = dims
+    _chk_tensor_on("probe_full_evaluate", "pivot", pivot, (dt + dp + cy,), torch.float32, a.device)
+    _chk_tensor_on("probe_full_evaluate", "beta", beta, (cy,), torch.float32, a.device)
+    _chk_tensor_on("probe_full_evaluate", "u", u, (cy, dt), torch.float32, a.device)
+    _chk_tensor_on("probe_full_evaluate", "v", v, (cy, dp), torch.float32, a.device)
+    _chk_tensor_on("probe_full_evaluate", "omega", omega, (cy, dt, dp), torch.float32, a.device)
+    _chk_tensor_on("probe_full_evaluate", "E", e, (cy, 3), torch.float64, a.device)
+    _chk_tensor_on("probe_full_evaluate", "n", n, (1,), torch.int64, a.device)
+    pred = torch.empty(b, t, p, cy, dtype=torch.float32, device=a.device) if want_pred else None
+    check(_lib.load().frl_probe_full_evaluate(*_probe_args(a, bs, y, mask, dims), _p(pivot), _p(beta), _p(u), _p(v), _p(omega), int(workgroups),
+                                              _p(e), _p(n), _p(pred), _p(ws), ws.numel(), _stream()), "frl_probe_full_evaluate")
+    return pred
+
+
 # ----------------------------------------------------------------------------------------------
 # EVT-stratified diagnostics (csrc/strata.hip)
 # ----------------------------------------------------------------------------------------------
