@@ -117,6 +117,22 @@ int frl_conv3x3_bwd_data_outmask(const void* dy, const void* y, int act, const f
 size_t frl_conv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout);
 int frl_conv3x3_bwd_weight(const void* dy, const void* y, int act, const void* x, float* dw, float* dbias, int B, int H,
                            int W, int Cin, int Cout, int dtype, void* ws, size_t ws_bytes, int flags, frl_stream_t stream);
+/* Up to 4 weight gradients over images of ONE shape [B][H][W] in one call (the three 3x3 convolutions of a smoothing block's backward):
+ * dy, y, x, dw, dbias, act, cin, cout are arrays of njobs entries; y[j] (with act[j] == 0), dw[j] and dbias[j] may be null.  Gradients
+ * are bit for bit those of frl_conv3x3_bwd_weight.  When every job is bf16 with H % 8 == 0, W % 32 == 0, Cin % 64 == 0 and Cout == 64,
+ * ONE launch of the band kernel serves all jobs in two cases (tiles = B * H / 8 * W / 32): the jobs' tiles together fit 256 workgroups
+ * (one tile per workgroup); or tiles >= 256 and the jobs have at most 8 64-channel chunks in all: every (job, chunk) gets 64 workgroups,
+ * workgroup k runs the four tile ranges that workgroups k, k + 64, k + 128, k + 192 of the single call own, each accumulated from zero,
+ * and adds them up in ONE slab in that order -- the chain in which the fixed-order reduction adds the single call's 256 slabs -- so a job
+ * leaves 64 slabs instead of 256 in its region of `ws`, reduced (deferrably) on their own.  Any other set of jobs runs job by job as
+ * frl_conv3x3_bwd_weight.  The workspace size depends on the route, so on frl_conv3x3_wgrad_multi: ask for it under the setting the
+ * call runs with. */
+size_t frl_conv3x3_bwd_weight_multi_workspace_bytes(int njobs, int B, int H, int W, const int* cin, const int* cout, int dtype);
+int frl_conv3x3_bwd_weight_multi(int njobs, const void* const* dy, const void* const* y, const int* act, const void* const* x,
+                                 float* const* dw, float* const* dbias, int B, int H, int W, const int* cin, const int* cout, int dtype,
+                                 void* ws, size_t ws_bytes, frl_stream_t stream);
+/* A/B hook: 0 = frl_conv3x3_bwd_weight_multi always runs job by job (default 1); returns the previous setting. */
+int frl_conv3x3_wgrad_multi(int on);
 /* Test / A-B hook (no reference counterpart): 1 routes every 3x3 weight gradient through the generic kernel instead of the bf16
  * band kernel; returns the previous setting. */
 int frl_conv3x3_wgrad_force_generic(int on);

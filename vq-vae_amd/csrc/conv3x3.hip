@@ -696,6 +696,12 @@ bool c3v_supported(int B, int H, int W, int Cin, int Cout, int dtype);
 int c3v_workgroups(int B, int H, int W);
 int c3v_launch(const void* dy, const void* ym, int act, const void* x, float* ws, int B, int H, int W, int Cin, int Cout, int oc_base,
                hipStream_t st);
+// several jobs of one image shape in one launch of the band kernel: eligibility, the workgroup split, the launch
+#define C3V_MAX_JOBS 4
+bool c3v_multi_supported(int njobs, int B, int H, int W, const int* cin, const int* cout, int dtype);
+int c3v_multi_split(int njobs, int B, int H, int W, const int* cin, int* nslab, int* tpw, int* nunits);
+int c3v_launch_multi(int njobs, const void* const* dy, const void* const* ym, const int* act, const void* const* x, float* const* slab, int B,
+                     int H, int W, const int* cin, const int* nslab, const int* tpw, const int* nunits, hipStream_t st);
 
 extern "C" {
 
@@ -790,6 +796,64 @@ int frl_conv3x3_bwd_weight(const void* dy, const void* y, int act, const void* x
                                                 Cout <= 64);      // (deferrable only when this is the call's single slice: the slices share `ws`)
   }
   return frl_check_launch("conv3x3_bwd_weight");
+}
+
+// Up to 4 weight gradients over images of one shape [B][H][W] (the three of a smoothing block's backward): dy / y / x / dw / dbias / act /
+// cin / cout are arrays of njobs entries; y[j], dw[j] and dbias[j] may be null.  Where c3v_multi_supported holds (bf16 band kernel,
+// Cout == 64, a split that keeps the single call's bits: conv3x3_wgrad.hip; frl_conv3x3_wgrad_multi on) ONE launch serves them all and
+// each job's slabs (a region of `ws` per job) are reduced by a job of their own; otherwise the jobs run one after the other as
+// frl_conv3x3_bwd_weight does, each on its region of `ws`.  Same gradient bits either way.
+size_t frl_conv3x3_bwd_weight_multi_workspace_bytes(int njobs, int B, int H, int W, const int* cin, const int* cout, int dtype) {
+  if (njobs < 1 || cin == nullptr || cout == nullptr) return 0;
+  size_t total = 0;
+  if (c3v_multi_supported(njobs, B, H, W, cin, cout, dtype)) {
+    int nwg[C3V_MAX_JOBS], tpw[C3V_MAX_JOBS], nun[C3V_MAX_JOBS];
+    c3v_multi_split(njobs, B, H, W, cin, nwg, tpw, nun);
+    for (int j = 0; j < njobs; ++j) total += (size_t)nwg[j] * ((size_t)64 * cin[j] * 9 + 64) * sizeof(float);
+  } else {
+    for (int j = 0; j < njobs; ++j) total += frl_conv3x3_bwd_weight_workspace_bytes(B, H, W, cin[j], cout[j]);
+  }
+  return total;
+}
+
+int frl_conv3x3_bwd_weight_multi(int njobs, const void* const* dy, const void* const* y, const int* act, const void* const* x, float* const* dw,
+                                 float* const* dbias, int B, int H, int W, const int* cin, const int* cout, int dtype, void* ws,
+                                 size_t ws_bytes, hipStream_t stream) {
+  if (njobs < 1 || dy == nullptr || y == nullptr || act == nullptr || x == nullptr || dw == nullptr || dbias == nullptr || cin == nullptr ||
+      cout == nullptr)
+    return frl_fail(-2, "conv3x3_bwd_weight_multi: needs at least one job and all per-job arrays");
+  for (int j = 0; j < njobs; ++j)
+    if (dy[j] == nullptr || x[j] == nullptr || cin[j] <= 0 || cout[j] <= 0) return frl_fail(-2, "conv3x3_bwd_weight_multi: a job without dy, x or channels");
+  if (ws == nullptr || ws_bytes < frl_conv3x3_bwd_weight_multi_workspace_bytes(njobs, B, H, W, cin, cout, dtype))
+    return frl_fail(-4, "conv3x3_bwd_weight_multi: workspace too small");
+  if (!c3v_multi_supported(njobs, B, H, W, cin, cout, dtype)) {
+    char* region = (char*)ws;
+    for (int j = 0; j < njobs; ++j) {
+      const size_t nb = frl_conv3x3_bwd_weight_workspace_bytes(B, H, W, cin[j], cout[j]);
+      if (dw[j] != nullptr || dbias[j] != nullptr) {
+        const int rc = frl_conv3x3_bwd_weight(dy[j], y[j], act[j], x[j], dw[j], dbias[j], B, H, W, cin[j], cout[j], dtype, region, nb, 0, stream);
+        if (rc) return rc;
+      }
+      region += nb;
+    }
+    return 0;
+  }
+  int nwg[C3V_MAX_JOBS], tpw[C3V_MAX_JOBS], nun[C3V_MAX_JOBS];               // nwg: the slabs of a job
+  c3v_multi_split(njobs, B, H, W, cin, nwg, tpw, nun);
+  const void* ym[C3V_MAX_JOBS];
+  float* slab[C3V_MAX_JOBS];
+  float* region = (float*)ws;
+  for (int j = 0; j < njobs; ++j) {
+    ym[j] = act[j] != FRL_ACT_NONE ? y[j] : nullptr;
+    slab[j] = region;
+    region += (size_t)nwg[j] * ((size_t)64 * cin[j] * 9 + 64);
+  }
+  const int rc = c3v_launch_multi(njobs, dy, ym, act, x, slab, B, H, W, cin, nwg, tpw, nun, stream);
+  if (rc) return rc;
+  for (int j = 0; j < njobs; ++j)
+    launch_slab_reduce_deferrable<float, C3Epi>((const float*)slab[j], nwg[j], (int64_t)64 * cin[j] * 9 + 64, C3Epi{64, cin[j] * 9, 0, 64, dw[j], dbias[j]},
+                                                stream);
+  return frl_check_launch("conv3x3_bwd_weight_multi");
 }
 
 }  // extern "C"

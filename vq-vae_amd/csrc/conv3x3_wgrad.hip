@@ -17,6 +17,7 @@
 // Output: per-workgroup float32 slabs in the layout of the generic kernel (tap-major), summed in a fixed order by slab_reduce_t.
 #include "frl_common.hpp"
 #include "frl_host.hpp"
+#include <string.h>
 #include <type_traits>
 
 #define C3V_TH 8
@@ -39,23 +40,51 @@ __device__ __forceinline__ bf16x8 c3v_tr8(const char* smem, int lo, int hi) {
   return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
-__global__ __launch_bounds__(512) void conv3x3_wgrad_band_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ Ymask, int mask_act,
-                                                                 const bf16* __restrict__ X, float* __restrict__ slab, int B, int H, int W,
-                                                                 int Cin, int Cout, int oc_base, int tiles_per_wg) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// One launch serves several weight gradients over images of one shape (B, H, W): a table of up to C3V_MAX_ENTRIES entries travels by
+// value in the kernel-argument segment (as FrlDeferTable, defer.hip); entry e owns the workgroups [first_wg, first_wg + nwg).
+// A UNIT is what one workgroup of the single call owns: `tiles_per_wg` consecutive tiles, accumulated from zero per 64-channel chunk.
+//   nunits == 1 (the single call; merged calls whose tiles all fit the grid): workgroup wg owns unit wg, all `ncks` chunks, slab wg.
+//   nunits  > 1 (merged call): workgroup wg owns the units wg, wg + unit_stride, ... and ONE chunk (ck_base); each unit is accumulated
+//   from zero and then added to slab wg in float32, in unit order: exactly the chain in which the fixed-order slab reduction adds the
+//   single call's slabs wg, wg + 64, wg + 128, wg + 192 (frl_reduce.hpp), so the reduced gradients keep the single call's bits.
+#define C3V_MAX_JOBS 4
+#define C3V_MAX_ENTRIES 8
+struct C3vJob {
+  const bf16* dY;
+  const bf16* Ymask;
+  const bf16* X;
+  float* slab;
+  int mask_act, Cin, Cout, oc_base, first_wg, nwg, tiles_per_wg, nunits, unit_stride, ck_base, ncks, pad_;
+};
+struct C3vTable {
+  int njobs, B, H, W;
+  C3vJob job[C3V_MAX_ENTRIES];
+};
+
+// the work of workgroup `wg` of one table entry (Cin: all input channels of the convolution = the channel stride of X and of the slab)
+__device__ __forceinline__ void c3v_band_body(const bf16* __restrict__ dY, const bf16* __restrict__ Ymask, int mask_act, const bf16* __restrict__ X,
+                                              float* __restrict__ slab, int B, int H, int W, int Cin, int Cout, int oc_base, int tiles_per_wg,
+                                              int nunits, int unit_stride, int ck_base, int ncks, int wg, char* smem) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, kc = lane >> 4;
   const int ib = wave & 3, og = wave >> 2;                       // 16 input channels of the 64-chunk; 32 output channels
   const int tiles_x = W / C3V_TW, tiles_y = H / C3V_TH;
   const int ntiles = B * tiles_x * tiles_y;
-  const int t_begin = blockIdx.x * tiles_per_wg;
+  const int t_begin = wg * tiles_per_wg;
   const int t_end = (t_begin + tiles_per_wg) < ntiles ? (t_begin + tiles_per_wg) : ntiles;
   const int ntl = t_end > t_begin ? t_end - t_begin : 0;
-  const int ncks = Cin >> 6;
-  const int nitems = ntl * ncks;                                 // item i: chunk i / ntl, tile t_begin + i % ntl
+  const bool units = nunits > 1;                                 // (uniform) several units, one chunk
+  int nitems = ntl * ncks;                                       // one unit: item i = chunk i / ntl, tile t_begin + i % ntl
+  if (units) {                                                   // several: item i = unit i / tiles_per_wg, its tile i % tiles_per_wg
+    nitems = 0;                                                  // (units are full up to the last busy one, then empty)
+    for (int t = 0; t < nunits; ++t) {
+      const int left = ntiles - (wg + t * unit_stride) * tiles_per_wg;
+      nitems += left < 0 ? 0 : (left < tiles_per_wg ? left : tiles_per_wg);
+    }
+  }
   const int64_t slab_n = (int64_t)64 * Cin * 9 + 64;
-  float* my = slab + (int64_t)blockIdx.x * slab_n;
+  float* my = slab + (int64_t)wg * slab_n;
 
   // ---- lane constants of the fragment reads: column (inside a row) of the lane's first pixel, window swizzle, 8-byte half ----
   int aoff[2][2], boff[3][2];                                    // [output block o][lo / hi], [dx][lo / hi]
@@ -76,8 +105,15 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_band_kernel(const bf16* __r
   }
 
   auto item_geom = [&](int i, int& b, int& y0, int& x0, int& ck) {
-    const int tile = t_begin + i % ntl;
-    ck = (i / ntl) << 6;
+    int tile;
+    if (units) {
+      const int t = i / tiles_per_wg;
+      tile = (wg + t * unit_stride) * tiles_per_wg + (i - t * tiles_per_wg);
+      ck = ck_base;
+    } else {
+      tile = t_begin + i % ntl;
+      ck = ck_base + ((i / ntl) << 6);
+    }
     b = tile / (tiles_x * tiles_y);
     const int tyx = tile % (tiles_x * tiles_y);
     y0 = (tyx / tiles_x) * C3V_TH;
@@ -161,6 +197,41 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_band_kernel(const bf16* __r
         acc[tap][o] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
   };
+  // a later unit of the workgroup: slab += accumulators, each lane on the addresses it stored itself (its earlier stores have been waited
+  // for; the loads are device-scope, past the CU's vector cache); float32 adds in unit order = the reduction's chain over the single
+  // call's slabs
+  auto add_chunk = [&](int ck) {
+    int lane_ = lane;
+    asm volatile("" : "+v"(lane_));
+    float* mine = my + (int64_t)(og * 32 + (lane_ >> 4) * 4) * Cin + ck + ib * 16 + (lane_ & 15);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+      for (int o = 0; o < 2; ++o) {
+        float old[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) old[r] = __hip_atomic_load(mine + ((int64_t)tap * 64 + o * 16 + r) * Cin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mine[((int64_t)tap * 64 + o * 16 + r) * Cin] = old[r] + acc[tap][o][r];
+        acc[tap][o] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+  };
+  auto write_bias = [&](bool first) {                            // column 0 of the "ones" product holds the row sums
+    if (ib == 0 && r16 == 0) {
+      float* mb = my + (int64_t)64 * Cin * 9 + og * 32 + kc * 4;
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = accb[o][r];
+          if (!first) v = __hip_atomic_load(mb + o * 16 + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + v;
+          mb[o * 16 + r] = v;
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < 2; ++o) accb[o] = f32x4{0.f, 0.f, 0.f, 0.f};
+  };
 
   if (nitems > 0) {
     dma_halo(0, 2 * C3V_DY_BYTES);
@@ -204,24 +275,36 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_band_kernel(const bf16* __r
         }
       }
     };
-    if (i < ntl && ib == 0) contract(std::true_type{});           // (uniform) the bias gradient rides with input chunk 0
+    if ((units ? ck_base == 0 : i < ntl) && ib == 0) contract(std::true_type{});   // (uniform) the bias gradient rides with input chunk 0
     else contract(std::false_type{});
     if (i + 1 < nitems) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // dY / Y registers and this wave's DMA pieces have landed
       commit_dy((cur ^ 1) * C3V_DY_BYTES);
     }
-    if ((i + 1) % ntl == 0) write_chunk((i / ntl) << 6);         // (uniform) last tile of an input-channel chunk
+    if (units) {                                                 // (uniform) last tile of a unit
+      if ((i + 1) % tiles_per_wg == 0 || i + 1 == nitems) {
+        if (i < tiles_per_wg) write_chunk(ck_base); else add_chunk(ck_base);
+        if (ck_base == 0) write_bias(i < tiles_per_wg);
+      }
+    } else if ((i + 1) % ntl == 0) write_chunk((i / ntl) << 6);  // (uniform) last tile of an input-channel chunk
     __syncthreads();
   }
+  if (units) return;
   if (nitems == 0) {                                             // a workgroup without tiles still owns a slab: zeros
     for (int ck = 0; ck < Cin; ck += 64) write_chunk(ck);
   }
-  if (ib == 0 && r16 == 0) {                                     // column 0 of the "ones" product holds the row sums
-#pragma unroll
-    for (int o = 0; o < 2; ++o)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) my[(int64_t)64 * Cin * 9 + (og * 2 + o) * 16 + kc * 4 + r] = accb[o][r];
-  }
+  write_bias(true);
+}
+
+__global__ __launch_bounds__(512) void conv3x3_wgrad_band_kernel(const C3vTable tab) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int j = 0;
+  while (j + 1 < tab.njobs && (int)blockIdx.x >= tab.job[j + 1].first_wg) ++j;     // block-uniform: scalar loads from the argument segment
+  const C3vJob& job = tab.job[j];
+  const int wg = (int)blockIdx.x - job.first_wg;
+  if (wg >= job.nwg) return;
+  c3v_band_body(job.dY, job.Ymask, job.mask_act, job.X, job.slab, tab.B, tab.H, tab.W, job.Cin, job.Cout, job.oc_base, job.tiles_per_wg, job.nunits,
+                job.unit_stride, job.ck_base, job.ncks, wg, smem);
 }
 
 // ---- host side (called from frl_conv3x3_bwd_weight, conv3x3.hip) ----
@@ -239,14 +322,88 @@ int c3v_launch(const void* dy, const void* ym, int act, const void* x, float* ws
   const int nwg = c3v_workgroups(B, H, W);
   const int tiles = B * (H / C3V_TH) * (W / C3V_TW);
   const int tpw = (tiles + nwg - 1) / nwg;
+  C3vTable tab;
+  memset(&tab, 0, sizeof(tab));
+  tab.njobs = 1; tab.B = B; tab.H = H; tab.W = W;
+  tab.job[0] = C3vJob{(const bf16*)dy, (const bf16*)ym, (const bf16*)x, ws, act, Cin, Cout, oc_base, 0, nwg, tpw, 1, 0, 0, Cin / 64, 0};
   auto kern = conv3x3_wgrad_band_kernel;
   FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3V_LDS));
-  FRL_LAUNCH_AS("conv3x3_wgrad_kernel", kern, dim3(nwg), dim3(512), C3V_LDS, st, (const bf16*)dy, (const bf16*)ym, act, (const bf16*)x, ws, B, H, W,
-                Cin, Cout, oc_base, tpw);
+  FRL_LAUNCH_AS("conv3x3_wgrad_kernel", kern, dim3(nwg), dim3(512), C3V_LDS, st, tab);
   return frl_check_launch("conv3x3_bwd_weight");
 }
 
+// ---- several weight gradients over images of one shape in ONE launch (frl_conv3x3_bwd_weight_multi, conv3x3.hip) ----
+// The split of the workgroup budget over the jobs, a function of the shapes alone (mirrored by frl_hip/wgrad_split.py), chosen so that
+// every reduced gradient keeps the bits of the single call; tiles = B * (H / 8) * (W / 32), budget 256 workgroups:
+//   * the jobs' tiles together fit the budget: every workgroup owns one tile and all chunks (nslab_j = tiles), as in the single call;
+//   * tiles >= 256 (the single call runs 256 workgroups of tpw = ceil(tiles / 256) tiles and reduces 256 slabs, in chains of four:
+//     k, k + 64, k + 128, k + 192): 64 workgroups per (job, 64-channel chunk), workgroup k runs those four units one after the other and
+//     adds them up in its slab in that order: nslab_j = 64, a quarter of the slabs, and items per workgroup = 4 * tpw for every job;
+//   * anything else (or more than 8 chunks in all) is no case for the merged launch.
+static int g_c3v_multi = 1;
+#define C3V_BUDGET 256
+#define C3V_CHAIN 4                          // slabs per chain of the reduction at 256 slabs (frl_reduce.hpp: k += 64)
+
+bool c3v_multi_supported(int njobs, int B, int H, int W, const int* cin, const int* cout, int dtype) {
+  if (!g_c3v_multi || njobs < 1 || njobs > C3V_MAX_JOBS) return false;
+  int chunks = 0;
+  for (int j = 0; j < njobs; ++j) {
+    if (cout[j] != 64 || !c3v_supported(B, H, W, cin[j], cout[j], dtype)) return false;
+    chunks += cin[j] / 64;
+  }
+  const int64_t tiles = (int64_t)B * (H / C3V_TH) * (W / C3V_TW);
+  return tiles * njobs <= C3V_BUDGET || (tiles >= C3V_BUDGET && chunks <= C3V_MAX_ENTRIES);
+}
+// -> grid; nslab / tpw / nunits [njobs] are written (call only where c3v_multi_supported holds)
+int c3v_multi_split(int njobs, int B, int H, int W, const int* cin, int* nslab, int* tpw, int* nunits) {
+  const int64_t tiles = (int64_t)B * (H / C3V_TH) * (W / C3V_TW);
+  int grid = 0;
+  for (int j = 0; j < njobs; ++j) {
+    if (tiles * njobs <= C3V_BUDGET) {
+      nslab[j] = (int)tiles; tpw[j] = 1; nunits[j] = 1;
+      grid += nslab[j];
+    } else {
+      nslab[j] = C3V_BUDGET / C3V_CHAIN; tpw[j] = (int)((tiles + C3V_BUDGET - 1) / C3V_BUDGET); nunits[j] = C3V_CHAIN;
+      grid += nslab[j] * (cin[j] / 64);
+    }
+  }
+  return grid;
+}
+int c3v_launch_multi(int njobs, const void* const* dy, const void* const* ym, const int* act, const void* const* x, float* const* slab, int B,
+                     int H, int W, const int* cin, const int* nslab, const int* tpw, const int* nunits, hipStream_t st) {
+  C3vTable tab;
+  memset(&tab, 0, sizeof(tab));
+  tab.B = B; tab.H = H; tab.W = W;
+  int e = 0, grid = 0;
+  const int64_t tiles = (int64_t)B * (H / C3V_TH) * (W / C3V_TW);
+  for (int j = 0; j < njobs; ++j) {
+    // every workgroup must own at least one tile: the kernel stores a slab only behind a unit's last tile, and the reduction reads all
+    // nslab slabs (tiles >= 256 gives >= 128 busy units for the 64 workgroups of a chained entry; one tile per workgroup otherwise)
+    if (nslab[j] < 1 || tpw[j] < 1 || (int64_t)(nslab[j] - 1) * tpw[j] >= tiles) return frl_fail(-2, "conv3x3_bwd_weight_multi: a workgroup without a tile");
+    const int parts = nunits[j] > 1 ? cin[j] / 64 : 1;             // several units: one table entry per 64-channel chunk
+    for (int q = 0; q < parts; ++q) {
+      if (e >= C3V_MAX_ENTRIES) return frl_fail(-2, "conv3x3_bwd_weight_multi: too many chunks for one launch");
+      tab.job[e++] = C3vJob{(const bf16*)dy[j], (const bf16*)ym[j], (const bf16*)x[j], slab[j], act[j], cin[j], 64, 0, grid, nslab[j], tpw[j],
+                            nunits[j], C3V_BUDGET / C3V_CHAIN, q * 64, nunits[j] > 1 ? 1 : cin[j] / 64, 0};
+      grid += nslab[j];
+    }
+  }
+  tab.njobs = e;
+  auto kern = conv3x3_wgrad_band_kernel;
+  FRL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C3V_LDS));
+  FRL_LAUNCH_AS("conv3x3_wgrad_multi_kernel", kern, dim3(grid), dim3(512), C3V_LDS, st, tab);
+  return frl_check_launch("conv3x3_bwd_weight_multi");
+}
+
 extern "C" {
+// A/B hook: 0 makes frl_conv3x3_bwd_weight_multi run its jobs one after the other through the single-call route (the bits of
+// frl_conv3x3_bwd_weight); default 1: one launch.  Returns the previous setting.
+int frl_conv3x3_wgrad_multi(int on) {
+  const int was = g_c3v_multi;
+  g_c3v_multi = on ? 1 : 0;
+  return was;
+}
+
 // Test / A-B hook: 1 routes every 3x3 weight gradient through the generic kernel of conv3x3.hip; returns the previous setting.
 int frl_conv3x3_wgrad_force_generic(int on) {
   const int was = g_c3v_off;

@@ -31,7 +31,7 @@ struct C3Epi {
       const int Cin = Cin9 / 9;
       const int tap = (int)(i / ((int64_t)OCT * Cin)), rem = (int)(i % ((int64_t)OCT * Cin));
       const int ocl = rem / Cin, ic = rem % Cin;
-      if (oc_base + ocl < Cout) dW[(int64_t)(oc_base + ocl) * Cin9 + ic * 9 + tap] = s;
+      if (dW != nullptr && oc_base + ocl < Cout) dW[(int64_t)(oc_base + ocl) * Cin9 + ic * 9 + tap] = s;
     } else if (dB != nullptr) {
       const int ocl = (int)(i - (int64_t)OCT * Cin9);
       if (oc_base + ocl < Cout) dB[oc_base + ocl] = s;

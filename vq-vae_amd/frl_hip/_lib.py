@@ -147,6 +147,9 @@ SIGNATURES = {
     "frl_conv3x3_bwd_data_blend": (c_int, [P, P, I, P, P, P, P, P, I, I, I, I, I, I, P, S, P]),
     "frl_conv3x3_bwd_weight_workspace_bytes": (S, [I, I, I, I, I]),
     "frl_conv3x3_bwd_weight": (c_int, [P, P, I, P, P, P, I, I, I, I, I, I, P, S, I, P]),
+    "frl_conv3x3_bwd_weight_multi_workspace_bytes": (S, [I, I, I, I, P, P, I]),
+    "frl_conv3x3_bwd_weight_multi": (c_int, [I, P, P, P, P, P, P, I, I, I, P, P, I, P, S, P]),
+    "frl_conv3x3_wgrad_multi": (c_int, [I]),
     "frl_sobel_fwd": (c_int, [P, P, I, I, I, I, I, P]),
     "frl_sobel_bwd": (c_int, [P, P, I, I, I, I, I, P]),
     "frl_sobel_bwd_add": (c_int, [P, P, P, I, I, I, I, I, P]),

@@ -285,9 +285,22 @@ class SpatialSmoothFn(Function):
         # a frozen convolution skips its weight-gradient launch (and a frozen bias its store); the 1x1 heads' kernel always writes all four
         wants = [(nig[1 + 2 * i], hb[i] and nig[2 + 2 * i]) for i in range(5)]      # (dW, db) of mb, a, b, g0, g2
 
+        # The three 3x3 weight gradients share ONE launch, issued last (their operands live until this node returns): the band kernel's
+        # workgroups are divided between them and each adds up four of the single call's slabs in the reduction's order: same bits, a
+        # quarter of the slabs.  The route is decided
+        # here from the saved tensors (every dy has the shape and dtype of its y); a frozen convolution contributes no job.
+        protos = {4: (gate_raw, g1), 3: (g1, res), 0: (feat, g)}
+        merged = [i for i in (4, 3, 0) if any(wants[i])]
+        merge = (len(merged) >= 2 and ops.fusion_enabled("wgradmulti")
+                 and ops.conv3x3_wgrad_multi_supported([(protos[i][0], protos[i][1], None, ACT_NONE, True, True) for i in merged]))
+        jobs = {}
+
         def wgrad3(i, dy_, x_, y_, a_):
             (ww, wb) = wants[i]
             if not (ww or wb):
+                return None, None
+            if merge:
+                jobs[i] = (dy_, x_, y_, a_, ww, wb)
                 return None, None
             dw_, db_ = ops.conv3x3_bwd_weight(dy_, x_, y_, a_, want_bias=wb)
             return _wanted(ctx, 1 + 2 * i, (dw_,))[0], db_
@@ -317,6 +330,10 @@ class SpatialSmoothFn(Function):
             dx = ops.sobel_bwd(ops.conv3x3_bwd_data(dfeat, w_mb, yf, af), add=dx)
         else:
             dx = None
+        if merge:
+            order = [i for i in merged if i in jobs]
+            res_ = dict(zip(order, ops.conv3x3_bwd_weight_multi([jobs[i] for i in order])))
+            (dw_g2, db_g2), (dw_g0, db_g0), (dw_mb, db_mb) = (res_.get(i, (None, None)) for i in (4, 3, 0))
         heads = _wanted(ctx, 3, (None if dw_a is None else dw_a.reshape(w_a.shape), db_a if hb[1] else None,
                                  None if dw_b is None else dw_b.reshape(w_b.shape), db_b if hb[2] else None))
         return (dx, dw_mb, db_mb if hb[0] else None) + heads + (dw_g0, db_g0 if hb[3] else None, dw_g2, db_g2 if hb[4] else None,

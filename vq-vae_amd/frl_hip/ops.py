@@ -1244,6 +1244,66 @@ def conv3x3_bwd_weight(dy, x, y=None, act: int = ACT_NONE, scalar_frags: bool = 
     return dw, db
 
 
+def conv3x3_wgrad_multi(on: bool) -> bool:
+    """A/B hook (include/frl_hip.h: frl_conv3x3_wgrad_multi): False makes conv3x3_bwd_weight_multi run job by job.  Returns the previous setting."""
+    return bool(_lib.load().frl_conv3x3_wgrad_multi(1 if on else 0))
+
+
+def conv3x3_wgrad_multi_supported(jobs) -> bool:
+    """True when the jobs [(dy, x, y, act, want_weight, want_bias), ...] can share ONE launch of the band kernel (csrc/conv3x3_wgrad.hip):
+    at most 4 contiguous bf16 jobs on one device over images of one shape, H % 8 == 0, W % 32 == 0, Cin % 64 == 0, Cout == 64, and a
+    tile count for which the merged launch keeps the single calls' bits (wgrad_split.eligible)."""
+    from . import wgrad_split
+    if not 1 <= len(jobs) <= wgrad_split.MAX_JOBS:
+        return False
+    dy0 = jobs[0][0]
+    for dy, x, y, act, _, _ in jobs:
+        ts = [t for t in (dy, x, y) if t is not None]
+        if any(t.dim() != 4 or not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous() or t.device != dy0.device for t in ts):
+            return False
+        if dy.shape[:3] != dy0.shape[:3] or x.shape[:3] != dy0.shape[:3] or (y is not None and y.shape != dy.shape):
+            return False
+        if act != ACT_NONE and y is None:
+            return False
+    b, h, w = dy0.shape[:3]
+    return wgrad_split.eligible(b, h, w, [j[1].shape[-1] for j in jobs], [j[0].shape[-1] for j in jobs])
+
+
+@_timed("conv3x3_bwd_weight_multi")
+def conv3x3_bwd_weight_multi(jobs):
+    """jobs: [(dy, x, y, act, want_weight, want_bias), ...] over images of one shape -> [(dw | None, db | None), ...] from one call
+    (frl_conv3x3_bwd_weight_multi): one launch of the band kernel where conv3x3_wgrad_multi_supported holds, else job by job."""
+    n = len(jobs)
+    dy0 = jobs[0][0]
+    b, h, wd = dy0.shape[:3]
+    for dy, x, y, act, ww, wb in jobs:
+        if dy.shape[:3] != dy0.shape[:3] or x.shape[:3] != dy0.shape[:3] or dy.dtype != dy0.dtype or x.dtype != dy0.dtype:
+            raise ValueError("conv3x3_bwd_weight_multi: the jobs share B, H, W and the dtype")
+        _chk_rows(dy, dy.shape[-1], "conv3x3_bwd_weight_multi.dy")
+        _chk_rows(x, x.shape[-1], "conv3x3_bwd_weight_multi.x")
+        if act != ACT_NONE:
+            if y is None:
+                raise ValueError("conv3x3_bwd_weight_multi: an activation mask needs y")
+            _chk_like(y, dy, "conv3x3_bwd_weight_multi.y")
+        if not (ww or wb):
+            raise ValueError("conv3x3_bwd_weight_multi: a job wants its weight gradient, its bias gradient or both")
+    lib = _lib.load()
+    cin = (ctypes.c_int * n)(*[j[1].shape[-1] for j in jobs])
+    cout = (ctypes.c_int * n)(*[j[0].shape[-1] for j in jobs])
+    acts = (ctypes.c_int * n)(*[int(j[3]) for j in jobs])
+    ws = workspace(lib.frl_conv3x3_bwd_weight_multi_workspace_bytes(n, b, h, wd, cin, cout, _dt(dy0)), dy0.device)
+    out = [(grad_empty((j[0].shape[-1], j[1].shape[-1], 3, 3), dy0.device) if j[4] else None,
+            grad_empty((j[0].shape[-1],), dy0.device) if j[5] else None) for j in jobs]
+
+    def ptrs(ts):
+        return (ctypes.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts])
+
+    check(lib.frl_conv3x3_bwd_weight_multi(n, ptrs([j[0] for j in jobs]), ptrs([j[2] if j[3] != ACT_NONE else None for j in jobs]), acts,
+                                           ptrs([j[1] for j in jobs]), ptrs([o[0] for o in out]), ptrs([o[1] for o in out]), b, h, wd, cin, cout,
+                                           _dt(dy0), _p(ws), ws.numel(), _stream()), "frl_conv3x3_bwd_weight_multi")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # fixed stencils of EdgeAwareSmoothingConv2D (csrc/stencil.hip)
 # ----------------------------------------------------------------------------------------------
